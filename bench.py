@@ -70,7 +70,17 @@ def parse():
     ap.add_argument("--no-families", action="store_true",
                     help="skip the `families` sub-record (the same measurement on the cube / layers / clusters clouds)")
     ap.add_argument("--no-host-align", action="store_true", help="skip the host-boundary timing (examples/bench_pcl_align.cpp)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, a fixed seeded sample of the larger arrays, at most 64 MB in all; configs 2-4)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.config == 5:
+        ap.error("--dump-outputs covers configs 2, 3 and 4")
+    return args
 
 
 def kernel_sources_sha():
@@ -184,6 +194,8 @@ def main():
     source_order_ms = icp.sourceOrderMs()
 
     steps, elapsed = timed_steps(icp, args.steps, args.warmup, fence, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, icp_outputs(icp, steps[-1], n))
 
     # a fresh frame: a NEW source cloud against the resident target -- its ordering, then one whole alignment (device times)
     fresh_frame = None
@@ -388,6 +400,8 @@ def run_pipeline(args, ctx, comm, tgt, src, n, rank, world, fence, gen_s):
         stage_ms["source_order"].append(icp.sourceOrderMs())
         info.update(filtered=(int(filt[0].shape[0]), int(filt[1].shape[0])), iterations=icp.nr_iterations_,
                     T=icp.getFinalTransformation(), wall_rest_ms=(t2 - t1) * 1e3)
+        if args.dump_outputs:
+            info.update(filt=filt, converged=icp.hasConverged())
 
     for _ in range(args.warmup):
         step()
@@ -402,6 +416,8 @@ def run_pipeline(args, ctx, comm, tgt, src, n, rank, world, fence, gen_s):
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipeline_outputs(info))
     from pcl_amd import synth
     vg_ms = float(np.mean(stage_ms["voxelgrid"]))
     achieved = B_ALG_VOXEL * 2 * n / (vg_ms * 1e-3) / 1e9
@@ -641,6 +657,65 @@ def cpu_baseline(args, mode, n, tgt, src):
                               "search_ms_per_iteration": round(ru["seconds_search"] / itu * 1e3, 2),
                               "search_speedup_over_one_thread": round(one / (ru["seconds_search"] / itu / n_sample), 1)}
     return out
+
+
+DUMP_SEED = 20251015            # the sample of the larger outputs is the same from run to run and from build to build
+DUMP_SAMPLE = 1 << 20           # rows kept of an output with more rows than this
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(n):
+    """Sorted indices of the fixed sample of an n-row output (all rows when n <= DUMP_SAMPLE)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def icp_outputs(icp, rec, n_src):
+    """Configs 2/3: what a caller of the timed path receives from its last step -- the step record (transformation, mse,
+    correspondence count, where the alignment stands) -- and the correspondences of that step's search for a sample of
+    the source points (target index, -1 where there is none, and the distance fetchCorrespondences reports)."""
+    q, m, d = icp.fetchCorrespondences()
+    match = np.full(n_src, -1.0)
+    match[q] = m
+    dist = np.full(n_src, np.nan, np.float32)
+    dist[q] = d
+    pick = dump_sample(n_src)
+    return {"final_transformation": rec["final_transformation"].astype(np.float32),
+            "mse": np.array([rec["mse"]], np.float64),
+            "num_correspondences": np.array([rec["num_correspondences"]], np.float64),
+            "iteration": np.array([rec["iteration"]], np.float64),
+            "alignment_ended": np.array([rec["alignment_ended"]], np.float64),
+            "source_sample_index": pick.astype(np.float64),
+            "match_index": match[pick],
+            "match_distance": dist[pick]}
+
+
+def pipeline_outputs(info):
+    """Config 4: the last pipeline step's filtered clouds (x, y, z, 1 rows; a sample of them when they are larger) and
+    its alignment."""
+    out = {"final_transformation": info["T"].astype(np.float32),
+           "iterations": np.array([info["iterations"]], np.float64),
+           "converged": np.array([info["converged"]], np.float64)}
+    for name, cloud in zip(("filtered_target", "filtered_source"), info["filt"]):
+        rows = cloud.cpu().numpy()
+        pick = dump_sample(len(rows))
+        out[name] = np.ascontiguousarray(rows[pick], np.float32)
+        out[name + "_count"] = np.array([len(rows)], np.float64)
+        if len(pick) < len(rows):
+            out[name + "_sample_index"] = pick.astype(np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, at most DUMP_MAX_BYTES in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("dumped %d outputs (%.1f MB) to %s" % (len(arrays), total / 2**20, directory), file=sys.stderr)
 
 
 def finish(out, rank, world):
