@@ -541,6 +541,74 @@ PCLHIP_API pclhip_status pclhip_icp_transform_source(pclhip_icp* icp, const floa
                                                      const void* in, void* out, size_t stride_bytes,
                                                      uint64_t n, size_t normals_offset_bytes);
 
+/* ---- GeneralizedIterativeClosestPoint -------------------------------------------------------------
+ * Replaces pcl::GeneralizedIterativeClosestPoint<PointXYZ, PointXYZ> with the Newton solver
+ * (registration/include/pcl/registration/gicp.h, impl/gicp.hpp:370-477,480-766,768-933).  Bound to a target index;
+ * the covariances (computeCovariances, impl/gicp.hpp:70-147) are computed by the first align() and cached until the
+ * source is set again (source) or the object is recreated on a new index (target), or replaced by the caller's.
+ * Not supported (refused by the bindings): useBFGS, source subsets (setIndices), multi-GPU. */
+typedef struct pclhip_gicp pclhip_gicp;
+typedef struct {
+  int max_iterations;                     /* gicp.h:146, default 200 */
+  double transformation_epsilon;          /* gicp.h:147, default 5e-4 */
+  double rotation_epsilon;                /* gicp.h:419 rotation_epsilon_, default 2e-3 */
+  double max_correspondence_distance;     /* gicp.h:148 corr_dist_threshold_, default 5 */
+  int min_number_correspondences;         /* gicp.h:149, default 4 */
+  int k_correspondences;                  /* gicp.h:409, default 20 (<= 32 here) */
+  double gicp_epsilon;                    /* gicp.h:413, default 1e-3 */
+  int max_inner_iterations;               /* gicp.h:429, default 20 */
+  double translation_gradient_tolerance;  /* gicp.h:425, default 1e-2 */
+  double rotation_gradient_tolerance;     /* gicp.h:427, default 1e-2 */
+} pclhip_gicp_params;
+typedef struct {
+  float final_transformation[16];   /* row-major: previous_transformation_ * guess (impl/gicp.hpp:905) */
+  float last_transformation[16];    /* transformation_ of the last outer iteration */
+  int nr_iterations;                /* outer iterations */
+  int converged;
+  uint64_t num_correspondences;     /* pairs of the last outer iteration */
+  int newton_iterations;            /* inner iterations, summed over the outer ones */
+  int newton_steps;                 /* line searches run (one multi-candidate pass each) */
+  int newton_steps_alpha_one;       /* ... of which accepted the full step (no gradient pass needed) */
+  int eval_passes;                  /* streaming passes over the pairs (candidate + gradient passes) */
+  int trace_count;                  /* entries written to the trace buffer */
+  int reserved;
+  double covariance_ms;             /* wall time of the covariances this call computed (0 when cached) */
+  double search_ms;                 /* GPU time of the 1-NN searches (HIP events) */
+  double pack_ms;                   /* ... of the pack passes (Mahalanobis matrices, cached sums) incl. their reductions */
+  double eval_ms;                   /* ... of the evaluation passes incl. their reductions */
+  double total_ms;                  /* wall time of the call (the rest: copies, launches, the host's serial step) */
+} pclhip_gicp_result;
+typedef struct {                    /* one entry per outer iteration (pclhip_gicp_set_trace) */
+  uint64_t correspondences;
+  int inner_iterations;
+  int reserved;
+  double f;                         /* the functor's value at the accepted x */
+  float transformation[16];         /* transformation_ after this iteration */
+} pclhip_gicp_trace;
+PCLHIP_API void pclhip_gicp_params_default(pclhip_gicp_params* p);
+PCLHIP_API pclhip_status pclhip_gicp_create(pclhip_index* target, pclhip_gicp** out);
+PCLHIP_API void pclhip_gicp_destroy(pclhip_gicp* gicp);
+/* setInputSource (gicp.h:160-166): stages the source and drops its covariances. */
+PCLHIP_API pclhip_status pclhip_gicp_set_source(pclhip_gicp* gicp, const void* points, size_t stride_bytes, uint64_t n);
+/* setSourceCovariances / setTargetCovariances (gicp.h:184-215): 9 doubles (row-major 3x3) per point in the cloud's
+ * order, host or device; used as given. */
+PCLHIP_API pclhip_status pclhip_gicp_set_source_covariances(pclhip_gicp* gicp, const double* cov, uint64_t n);
+PCLHIP_API pclhip_status pclhip_gicp_set_target_covariances(pclhip_gicp* gicp, const double* cov, uint64_t n);
+/* Optional per-outer-iteration record of the next alignments (NULL / 0: none); the buffer must outlive them. */
+PCLHIP_API pclhip_status pclhip_gicp_set_trace(pclhip_gicp* gicp, pclhip_gicp_trace* buf, int capacity);
+/* computeTransformation (impl/gicp.hpp:768-930).  guess: row-major 4x4 or NULL. */
+PCLHIP_API pclhip_status pclhip_gicp_align(pclhip_gicp* gicp, const pclhip_gicp_params* params, const float guess[16],
+                                          pclhip_gicp_result* result);
+/* OptimizationFunctorWithIndices::dfddf (impl/gicp.hpp:612-750) on the pairs of the last outer iteration: f (the
+ * functor's value), gradient g[6], Hessian H[36] row-major (exposed for tests). */
+PCLHIP_API pclhip_status pclhip_gicp_evaluate(pclhip_gicp* gicp, const double x[6], double* f, double g[6], double H[36]);
+/* mahalanobis_ (impl/gicp.hpp:863-865): 9 doubles per source point, original order (NaN for non-finite points). */
+PCLHIP_API pclhip_status pclhip_gicp_mahalanobis(pclhip_gicp* gicp, double* out);
+/* Registration::getFitnessScore (impl/registration.hpp:132-168) through pclhip_icp_fitness_score; T NULL: the final
+ * transformation of the last alignment. */
+PCLHIP_API pclhip_status pclhip_gicp_fitness_score(pclhip_gicp* gicp, const float T[16], double max_range, double* score,
+                                                  uint64_t* nr);
+
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/
  * voxel_grid.hpp:597-814) with downsample_all_data and the optional pass-through filter in front of

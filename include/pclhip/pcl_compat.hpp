@@ -34,6 +34,7 @@
 #include <cstring>
 #include <limits>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <typeinfo>
 #include <type_traits>
@@ -1194,6 +1195,123 @@ class IterativeClosestPointWithNormals : public IterativeClosestPoint<PointSourc
  protected:
   bool enforceSameDirectionNormals() const override { return enforce_same_direction_normals_; }
   bool use_symmetric_objective_ = false, enforce_same_direction_normals_ = true;
+};
+
+// pcl::GeneralizedIterativeClosestPoint<PointSource, PointTarget> with the Newton solver (registration/include/pcl/
+// registration/gicp.h, impl/gicp.hpp:370-477, 768-933) on the C ABI's pclhip_gicp: covariances computed by the first
+// align() and cached (setInputSource drops the source's, setInputTarget the target's), or the caller's.  useBFGS, source
+// subsets (setIndices) are refused with std::logic_error.
+template <typename PointSource, typename PointTarget>
+class GeneralizedIterativeClosestPoint : public IterativeClosestPoint<PointSource, PointTarget> {
+  using Base = IterativeClosestPoint<PointSource, PointTarget>;
+ public:
+  using PointCloudSource = typename Base::PointCloudSource;
+  using Matrix4 = typename Base::Matrix4;
+  using PointCloudSourceConstPtr = typename Registration<PointSource, PointTarget>::PointCloudSourceConstPtr;
+  using PointCloudTargetConstPtr = typename Registration<PointSource, PointTarget>::PointCloudTargetConstPtr;
+  using MatricesVector = std::vector<std::array<double, 9>>;  // gicp.h:104 (Eigen::Matrix3d each; row-major here)
+  using MatricesVectorPtr = std::shared_ptr<MatricesVector>;
+  using Ptr = std::shared_ptr<GeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+  GeneralizedIterativeClosestPoint() : GeneralizedIterativeClosestPoint(Context::defaultContext()) {}
+  explicit GeneralizedIterativeClosestPoint(Context::Ptr ctx) : Base(std::move(ctx)) {  // gicp.h:136-152
+    this->reg_name_ = "GeneralizedIterativeClosestPoint";
+    pclhip_gicp_params_default(&p_);
+    this->max_iterations_ = p_.max_iterations;
+    this->transformation_epsilon_ = p_.transformation_epsilon;
+    this->corr_dist_threshold_ = p_.max_correspondence_distance;
+    this->min_number_correspondences_ = p_.min_number_correspondences;
+  }
+  ~GeneralizedIterativeClosestPoint() override { if (gicp_) pclhip_gicp_destroy(gicp_); }
+
+  void setInputSource(const PointCloudSourceConstPtr& cloud) override {  // gicp.h:160-166
+    src_cov_.reset();
+    Base::setInputSource(cloud);
+  }
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // gicp.h:174-180
+    tgt_cov_.reset();
+    if (gicp_) { pclhip_gicp_destroy(gicp_); gicp_ = nullptr; }
+    Base::setInputTarget(cloud);
+  }
+  void setSourceCovariances(const MatricesVectorPtr& c) { src_cov_ = c; src_cov_dirty_ = true; }  // gicp.h:184-199
+  void setTargetCovariances(const MatricesVectorPtr& c) { tgt_cov_ = c; tgt_cov_dirty_ = true; }  // :201-215
+  void setIndices(const IndicesPtr& indices) override { refuseIndices(indices != nullptr); }
+  void setIndices(const IndicesConstPtr& indices) override { refuseIndices(indices != nullptr); }
+  void useBFGS() { throw std::logic_error("GeneralizedIterativeClosestPoint: the BFGS solver is not supported (Newton only)"); }
+  // gicp.h:386-431
+  void setRotationEpsilon(double e) { p_.rotation_epsilon = e; }
+  double getRotationEpsilon() const { return p_.rotation_epsilon; }
+  void setCorrespondenceRandomness(int k) { p_.k_correspondences = k; }
+  int getCorrespondenceRandomness() const { return p_.k_correspondences; }
+  void setMaximumOptimizerIterations(int n) { p_.max_inner_iterations = n; }
+  int getMaximumOptimizerIterations() const { return p_.max_inner_iterations; }
+  void setTranslationGradientTolerance(double t) { p_.translation_gradient_tolerance = t; }
+  double getTranslationGradientTolerance() const { return p_.translation_gradient_tolerance; }
+  void setRotationGradientTolerance(double t) { p_.rotation_gradient_tolerance = t; }
+  double getRotationGradientTolerance() const { return p_.rotation_gradient_tolerance; }
+  // the last alignment's record: Newton iterations, passes, covariance time
+  const pclhip_gicp_result& lastResult() const { return result_; }
+
+  // Registration::getFitnessScore (impl/registration.hpp:132-168)
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
+    double score = std::numeric_limits<double>::max();
+    if (!this->initCompute() || !ensureGicp()) return score;
+    pclhip_gicp_fitness_score(gicp_, this->final_transformation_.m, max_range, &score, nullptr);
+    return score;
+  }
+
+ protected:
+  void refuseIndices(bool given) {
+    if (given) throw std::logic_error("GeneralizedIterativeClosestPoint: source subsets (setIndices) are not supported");
+  }
+  bool ensureGicp() {
+    pclhip_index* ix = this->tree_->handle();
+    if (gicp_ && (gicp_target_ != ix || this->target_built_)) { pclhip_gicp_destroy(gicp_); gicp_ = nullptr; }
+    this->target_built_ = false;
+    if (!gicp_) {
+      if (pclhip_gicp_create(ix, &gicp_) != PCLHIP_OK) return false;
+      gicp_target_ = ix;
+      this->source_cloud_updated_ = true;
+      tgt_cov_dirty_ = tgt_cov_ != nullptr;
+    }
+    if (this->source_cloud_updated_) {
+      if (pclhip_gicp_set_source(gicp_, this->input_->points.data(), sizeof(PointSource), this->input_->size()) != PCLHIP_OK)
+        return false;
+      this->source_cloud_updated_ = false;
+      src_cov_dirty_ = src_cov_ != nullptr;
+    }
+    if (src_cov_dirty_ && src_cov_) {
+      if (pclhip_gicp_set_source_covariances(gicp_, src_cov_->front().data(), src_cov_->size()) != PCLHIP_OK) return false;
+      src_cov_dirty_ = false;
+    }
+    if (tgt_cov_dirty_ && tgt_cov_) {
+      if (pclhip_gicp_set_target_covariances(gicp_, tgt_cov_->front().data(), tgt_cov_->size()) != PCLHIP_OK) return false;
+      tgt_cov_dirty_ = false;
+    }
+    return true;
+  }
+  void computeTransformation(PointCloudSource& output, const Matrix4& guess) override {  // impl/gicp.hpp:768-930
+    this->converged_ = false;
+    if (!ensureGicp()) return;
+    p_.max_iterations = this->max_iterations_;
+    p_.transformation_epsilon = this->transformation_epsilon_;
+    p_.max_correspondence_distance = this->corr_dist_threshold_;
+    p_.min_number_correspondences = this->min_number_correspondences_;
+    if (pclhip_gicp_align(gicp_, &p_, guess.m, &result_) != PCLHIP_OK) return;
+    std::memcpy(this->final_transformation_.m, result_.final_transformation, sizeof result_.final_transformation);
+    std::memcpy(this->transformation_.m, result_.last_transformation, sizeof result_.last_transformation);
+    this->converged_ = result_.converged != 0;
+    this->nr_iterations_ = result_.nr_iterations;
+    output = *this->input_;  // :929: transformPointCloud(*input_, output, final_transformation_)
+    pclhip_transform_cloud(this->ctx_->get(), this->final_transformation_.m, 1, output.points.data(), output.points.data(),
+                           sizeof(PointSource), output.size(), 0);
+  }
+
+  pclhip_gicp_params p_;
+  pclhip_gicp_result result_ = {};
+  pclhip_gicp* gicp_ = nullptr;
+  pclhip_index* gicp_target_ = nullptr;
+  MatricesVectorPtr src_cov_, tgt_cov_;
+  bool src_cov_dirty_ = false, tgt_cov_dirty_ = false;
 };
 
 // pcl::io::loadPCDFile / savePCDFile{ASCII,Binary,BinaryCompressed} (io/include/pcl/io/pcd_io.h:685-800)

@@ -53,6 +53,27 @@ class IcpStep(C.Structure):
                 ("final_transformation", C.c_float * 16)]
 
 
+class GicpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("max_correspondence_distance", C.c_double), ("min_number_correspondences", C.c_int),
+                ("k_correspondences", C.c_int), ("gicp_epsilon", C.c_double), ("max_inner_iterations", C.c_int),
+                ("translation_gradient_tolerance", C.c_double), ("rotation_gradient_tolerance", C.c_double)]
+
+
+class GicpResult(C.Structure):
+    _fields_ = [("final_transformation", C.c_float * 16), ("last_transformation", C.c_float * 16),
+                ("nr_iterations", C.c_int), ("converged", C.c_int), ("num_correspondences", C.c_uint64),
+                ("newton_iterations", C.c_int), ("newton_steps", C.c_int), ("newton_steps_alpha_one", C.c_int),
+                ("eval_passes", C.c_int), ("trace_count", C.c_int), ("reserved", C.c_int),
+                ("covariance_ms", C.c_double), ("search_ms", C.c_double), ("pack_ms", C.c_double),
+                ("eval_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class GicpTrace(C.Structure):
+    _fields_ = [("correspondences", C.c_uint64), ("inner_iterations", C.c_int), ("reserved", C.c_int),
+                ("f", C.c_double), ("transformation", C.c_float * 16)]
+
+
 class ConvergenceState(C.Structure):
     _fields_ = [("prev_mse", C.c_double), ("iterations_similar_transforms", C.c_int), ("convergence_state", C.c_int)]
 
@@ -115,6 +136,19 @@ SIGNATURES = {
                                     C.POINTER(_u64)]),
     "pclhip_gicp_covariances": (C.c_int, [_vp, C.c_int, C.c_double, _vp]),
     "pclhip_index_set_normals": (C.c_int, [_vp, _vp, _sz]),
+    "pclhip_gicp_params_default": (None, [C.POINTER(GicpParams)]),
+    "pclhip_gicp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "pclhip_gicp_destroy": (None, [_vp]),
+    "pclhip_gicp_set_source": (C.c_int, [_vp, _vp, _sz, _u64]),
+    "pclhip_gicp_set_source_covariances": (C.c_int, [_vp, _vp, _u64]),
+    "pclhip_gicp_set_target_covariances": (C.c_int, [_vp, _vp, _u64]),
+    "pclhip_gicp_set_trace": (C.c_int, [_vp, C.POINTER(GicpTrace), C.c_int]),
+    "pclhip_gicp_align": (C.c_int, [_vp, C.POINTER(GicpParams), C.POINTER(C.c_float), C.POINTER(GicpResult)]),
+    "pclhip_gicp_evaluate": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]),
+    "pclhip_gicp_mahalanobis": (C.c_int, [_vp, _vp]),
+    "pclhip_gicp_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
+                                            C.POINTER(_u64)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

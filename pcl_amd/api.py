@@ -1145,6 +1145,225 @@ def savePCDFile(path, cloud, mode="binary", precision=8, width=None, height=None
                                                  _fp(vp) if vp is not None else None, data_type, int(precision)))
 
 
+class GeneralizedIterativeClosestPoint:
+    """pcl::GeneralizedIterativeClosestPoint<PointXYZ, PointXYZ> with the Newton solver (registration/include/pcl/
+    registration/gicp.h, impl/gicp.hpp:370-477, 768-933).  Covariances are computed by the first align() and cached:
+    setInputSource drops the source's, setInputTarget the target's; set{Source,Target}Covariances replace them."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.p = _lib.GicpParams()
+        self.lib.pclhip_gicp_params_default(C.byref(self.p))
+        self.tree = KdTree(self.ctx)
+        self.src_tree = None
+        self.h = None
+        self.src = None
+        self.target = None
+        self._target_updated = False
+        self._force_no_recompute = False
+        self._src_dirty = True
+        self._src_cov = None
+        self._tgt_cov = None
+        self._tgt_cov_dirty = False
+        self.result = None
+        self.trace = []
+        self.ctx._adopt(self)
+
+    def _release(self):
+        self._drop()
+
+    def _drop(self):
+        if getattr(self, "h", None):
+            if self.ctx.h is not None:
+                self.lib.pclhip_gicp_destroy(self.h)
+            self.h = None
+        self._src_dirty = True
+        self._tgt_cov_dirty = self._tgt_cov is not None
+
+    def getClassName(self):
+        return "GeneralizedIterativeClosestPoint"
+
+    # --- inputs (gicp.h:160-215, registration.h:195-240) ---
+    def setInputTarget(self, cloud):
+        """GeneralizedIterativeClosestPoint::setInputTarget (gicp.h:174-180): drops the target covariances."""
+        self.target = cloud
+        self._target_updated = True
+        self._tgt_cov = None
+        self._drop()
+
+    def setSearchMethodTarget(self, tree, force_no_recompute=False):
+        """registration.h:214-221: a new tree counts as an update of the target; with force_no_recompute the caller
+        vouches that `tree` already indexes it and it is used as given."""
+        self.tree = tree
+        self._force_no_recompute = bool(force_no_recompute)
+        self._target_updated = self.target is not None
+        self._drop()
+
+    def setSearchMethodSource(self, tree, force_no_recompute=False):
+        """registration.h:228-240: the source tree only serves the source covariances, which are computed over the
+        source cloud itself here (the same k nearest neighbours whichever tree finds them)."""
+        self.src_tree = tree
+
+    def setInputSource(self, cloud):
+        """GeneralizedIterativeClosestPoint::setInputSource (gicp.h:160-166): drops the source covariances."""
+        self.src = cloud
+        self._src_cov = None
+        self._src_dirty = True
+
+    def setSourceCovariances(self, cov):
+        self._src_cov = np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+        self._src_dirty = True
+
+    def setTargetCovariances(self, cov):
+        self._tgt_cov = np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+        self._tgt_cov_dirty = True
+
+    def setIndices(self, indices):
+        if indices is not None:
+            raise NotImplementedError("GeneralizedIterativeClosestPoint: source subsets (setIndices) are not supported")
+
+    def useBFGS(self):
+        raise NotImplementedError("GeneralizedIterativeClosestPoint: the BFGS solver is not supported (Newton only)")
+
+    def setCommunicator(self, comm):
+        raise NotImplementedError("GeneralizedIterativeClosestPoint: multi-GPU registration is not supported")
+
+    # --- parameters (gicp.h:136-152, 386-431) ---
+    def setMaximumIterations(self, n):
+        self.p.max_iterations = int(n)
+
+    def setTransformationEpsilon(self, e):
+        self.p.transformation_epsilon = float(e)
+
+    def setRotationEpsilon(self, e):
+        self.p.rotation_epsilon = float(e)
+
+    def setMaxCorrespondenceDistance(self, d):
+        self.p.max_correspondence_distance = float(d)
+
+    def setCorrespondenceRandomness(self, k):
+        self.p.k_correspondences = int(k)
+
+    def setMaximumOptimizerIterations(self, n):
+        self.p.max_inner_iterations = int(n)
+
+    def setTranslationGradientTolerance(self, t):
+        self.p.translation_gradient_tolerance = float(t)
+
+    def setRotationGradientTolerance(self, t):
+        self.p.rotation_gradient_tolerance = float(t)
+
+    def getMaximumIterations(self):
+        return int(self.p.max_iterations)
+
+    def getTransformationEpsilon(self):
+        return float(self.p.transformation_epsilon)
+
+    def getRotationEpsilon(self):
+        return float(self.p.rotation_epsilon)
+
+    def getMaxCorrespondenceDistance(self):
+        return float(self.p.max_correspondence_distance)
+
+    def getCorrespondenceRandomness(self):
+        return int(self.p.k_correspondences)
+
+    def getMaximumOptimizerIterations(self):
+        return int(self.p.max_inner_iterations)
+
+    def _ensure(self):
+        if self._target_updated and not self._force_no_recompute:
+            self.tree.setInputCloud(self.target)
+            self._target_updated = False
+            self._drop()
+        if self.tree.h is None:
+            raise ValueError("No input target dataset was given!")
+        if self.src is None:
+            raise ValueError("No input source dataset was given!")
+        if self.h is None:
+            h = C.c_void_p()
+            check(self.lib.pclhip_gicp_create(self.tree.h, C.byref(h)), self.ctx.h)
+            self.h = h
+        if self._src_dirty:
+            ptr, stride, n, keep = _cloud(self.src)
+            check(self.lib.pclhip_gicp_set_source(self.h, ptr, stride, n), self.ctx.h)
+            if self._src_cov is not None:
+                check(self.lib.pclhip_gicp_set_source_covariances(self.h, C.c_void_p(self._src_cov.ctypes.data),
+                                                                  len(self._src_cov)), self.ctx.h)
+            self._src_dirty = False
+        if self._tgt_cov_dirty:
+            check(self.lib.pclhip_gicp_set_target_covariances(self.h, C.c_void_p(self._tgt_cov.ctypes.data),
+                                                              len(self._tgt_cov)), self.ctx.h)
+            self._tgt_cov_dirty = False
+
+    def align(self, guess=None, trace_capacity=256):
+        """Registration::align -> computeTransformation (impl/gicp.hpp:768-930).  Results via getFinalTransformation()
+        / hasConverged(); the per-outer-iteration record in self.trace."""
+        self._ensure()
+        buf = (_lib.GicpTrace * max(1, int(trace_capacity)))()
+        check(self.lib.pclhip_gicp_set_trace(self.h, buf, int(trace_capacity)), self.ctx.h)
+        r = _lib.GicpResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16)
+        try:
+            check(self.lib.pclhip_gicp_align(self.h, C.byref(self.p), _fp(g) if g is not None else None, C.byref(r)),
+                  self.ctx.h)
+        finally:
+            self.lib.pclhip_gicp_set_trace(self.h, None, 0)
+        self.result = r
+        self.trace = [dict(correspondences=int(t.correspondences), inner_iterations=int(t.inner_iterations), f=float(t.f),
+                           transformation=np.array(t.transformation, np.float32).reshape(4, 4))
+                      for t in buf[:r.trace_count]]
+
+    def getFinalTransformation(self):
+        return np.array(self.result.final_transformation, np.float32).reshape(4, 4)
+
+    def getLastIncrementalTransformation(self):
+        return np.array(self.result.last_transformation, np.float32).reshape(4, 4)
+
+    def hasConverged(self):
+        return bool(self.result.converged)
+
+    @property
+    def nr_iterations_(self):
+        return int(self.result.nr_iterations)
+
+    def getFitnessScore(self, max_range=float(np.finfo(np.float64).max)):
+        """Registration::getFitnessScore (impl/registration.hpp:132-168) with the final transformation."""
+        self._ensure()
+        T = np.ascontiguousarray(self.getFinalTransformation(), np.float32).reshape(16)
+        score = C.c_double(0.0)
+        nr = C.c_uint64(0)
+        check(self.lib.pclhip_gicp_fitness_score(self.h, _fp(T), C.c_double(max_range), C.byref(score), C.byref(nr)),
+              self.ctx.h)
+        return float(score.value)
+
+    def evaluate(self, x):
+        """OptimizationFunctorWithIndices::dfddf (impl/gicp.hpp:612-750) on the pairs of the last outer iteration:
+        (f, g[6], H[6x6])."""
+        xv = np.ascontiguousarray(x, np.float64).reshape(6)
+        f = C.c_double(0.0)
+        g = np.zeros(6, np.float64)
+        H = np.zeros(36, np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self.lib.pclhip_gicp_evaluate(self.h, xv.ctypes.data_as(dp), C.byref(f), g.ctypes.data_as(dp),
+                                            H.ctypes.data_as(dp)), self.ctx.h)
+        return float(f.value), g, H.reshape(6, 6)
+
+    def mahalanobis(self):
+        """mahalanobis_: one 3x3 per source point (NaN for non-finite points)."""
+        n = _cloud(self.src)[2]
+        out = np.zeros((n, 9), np.float64)
+        check(self.lib.pclhip_gicp_mahalanobis(self.h, C.c_void_p(out.ctypes.data)), self.ctx.h)
+        return out.reshape(n, 3, 3)
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+
 class VoxelGrid:
     """pcl::VoxelGrid<PointT> for pcl::PointXYZ ((n, 4) clouds) and pcl::PointNormal ((n, 12) clouds): leaf size,
     minimum points per voxel, downsample_all_data, the pass-through filter on one field, the leaf layout."""

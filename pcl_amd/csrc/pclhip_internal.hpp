@@ -341,6 +341,10 @@ struct pclhip_icp {
   uint32_t* lane_bcount = nullptr;
   uint32_t* lane_queue = nullptr;
   uint32_t* lane_tot = nullptr;
+  // a GeneralizedIterativeClosestPoint drives this registration's search (gicp.hpp): the transform order of its search
+  // launches (-1: the mode's) and no accumulation behind them
+  int order_override = -1;
+  bool search_only = false;
 };
 
 namespace pclhip {

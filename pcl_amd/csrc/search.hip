@@ -2031,7 +2031,7 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
   for (int i = 0; i < 12; ++i) M.m[i] = T ? T[i] : 0.0f;
   // clouds with normals move through transformPointCloudWithNormals (Transformer order), plain clouds
   // through Matrix4f * Vector4f (impl/icp.hpp:49-111)
-  const int order = (mode == PCLHIP_ICP_POINT_TO_POINT) ? 0 : 1;
+  const int order = icp->order_override >= 0 ? icp->order_override : ((mode == PCLHIP_ICP_POINT_TO_POINT) ? 0 : 1);
   // candidates must be <= max_d2 (a float): strict bound just above it; +inf when unbounded
   const float bound = use_max ? std::nextafterf(max_d2, __builtin_inff()) : __builtin_inff();
   uint32_t ngroups = (icp->n + WAVE - 1) / WAVE;
@@ -2135,6 +2135,11 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
     }
     (void)hipEventRecord(device_loop ? ev[1] : icp->ev_mid, s);
     icp->mid_recorded = true;
+    if (icp->search_only && !device_loop) {  // GeneralizedIterativeClosestPoint: its own passes follow (gicp.hpp)
+      (void)hipEventRecord(icp->ev1, s);
+      PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+      return PCLHIP_OK;
+    }
     const uint8_t* keep = nullptr;
     if (filters) {
       pclhip_status st = apply_correspondence_filters(icp, max_d2, use_max);
@@ -2347,3 +2352,5 @@ void preload_search_kernels(pclhip_ctx* ctx) {
 }
 
 }  // namespace pclhip
+
+#include "gicp.hpp"  // GeneralizedIterativeClosestPoint: its kernels and entry points, on this file's search
