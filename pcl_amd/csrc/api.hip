@@ -735,6 +735,7 @@ void pclhip_index_destroy(pclhip_index* ix) {
   if (ix->pts && !ix->pts_borrowed) (void)dev_free(ix->ctx, ix->pts);
   if (ix->soa) (void)dev_free(ix->ctx, ix->soa);
   if (ix->nrm) (void)dev_free(ix->ctx, ix->nrm);
+  if (ix->plane) (void)dev_free(ix->ctx, ix->plane);
   if (ix->disc) (void)dev_free(ix->ctx, ix->disc);
   if (ix->rank) (void)dev_free(ix->ctx, ix->rank);
   if (ix->lv_dev) (void)dev_free(ix->ctx, ix->lv_dev);
@@ -1292,6 +1293,8 @@ pclhip_status pclhip_index_set_normals(pclhip_index* ix, const void* normals, si
   hipLaunchKernelGGL(gather_normals_kernel, dim3((ix->n_pad + 255) / 256), dim3(256), 0, ctx->stream, dn, stride,
                      ix->pts, ix->n, ix->n_pad, ix->nrm);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+  st = launch_plane_records(ix);
+  if (st != PCLHIP_OK) return st;
   PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ix->has_normals = true;
   return PCLHIP_OK;

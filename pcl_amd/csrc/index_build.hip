@@ -2035,6 +2035,7 @@ pclhip::IndexView pclhip_index::view() const {
   v.pts = pts;
   v.soa = soa;
   v.nrm = nrm;
+  v.plane = plane;
   v.disc = disc;
   v.disc_from = 4.0f * leaf_diag2;  // stand-off (squared, in leaf diagonals squared) from which discs replace boxes
   v.lv = lv_dev;

@@ -8,6 +8,8 @@
 //                           wavefront stages in LDS with global_load_lds_dwordx4; candidate pairs
 //                           then feed v_pk_* math from broadcast ds_read_b128.
 //   nrm   [n_pad]  float4   (nx,ny,nz,curvature) in the same order (optional).
+//   plane [n_pad]  float4   (nx,ny,nz,c) with c = fl(fl(fl(nx*x)+fl(ny*y))+fl(nz*z)), present with nrm: the point-to-plane
+//                           accumulation gathers this one record per pair instead of pts + nrm (launch_plane_records).
 //   box[1][n1]     Box      tight AABB of every leaf = LEAF consecutive sorted points.
 //   box[l][n_l]    Box      AABB of FANOUT consecutive boxes of level l-1 (implicit wide BVH:
 //                           no pointers, child c of node i at level l is node i*FANOUT+c of l-1).
@@ -75,6 +77,9 @@ struct IndexView {
   // also where the box is thin (a flat piece of a surface: the box is as thick as the noise, the cell is unbounded)
   const Box* cell2;
   const Box* cell3;
+  // (nx, ny, nz, n.t) of every point, written with nrm (launch_plane_records); nullptr without normals.  Last: the search
+  // kernels' arguments keep their offsets.
+  const float4* plane;
 };
 
 // The per-lane search structure (lane_search.hpp; round 5): the same kd order seen as an implicit 4-ary tree over the
@@ -240,6 +245,7 @@ struct pclhip_index {
   bool pts_borrowed = false;  // pts belongs to somebody else (build_index_over): not freed with the index
   float* soa = nullptr;
   float4* nrm = nullptr;
+  float4* plane = nullptr;  // refreshed by every writer of nrm (launch_plane_records), freed with it
   float4* disc = nullptr;
   float leaf_diag2 = 0.0f;  // mean squared diagonal of the leaf boxes
   float disc_thickness = 1.0f;  // sum of the discs' half thicknesses / sum of their radii: how thin the leaves are
@@ -459,6 +465,8 @@ pclhip_status launch_estimate_pairs(pclhip_ctx* ctx, int mode, const float4* src
                                     const float4* tgt, const float4* tgt_nrm, const float* weights, uint32_t n, bool enforce,
                                     double* sums);
 pclhip_status launch_normals_radius(pclhip_index* ix, double radius, const float vp[3], uint64_t* nan_count);
+// plane[] from nrm[] and pts[] (stream-ordered): every writer of ix->nrm calls it after its last write
+pclhip_status launch_plane_records(pclhip_index* ix);
 // normals at arbitrary query points (Feature::setSearchSurface): `queries` dense float4 in slot order; the radius form
 // takes them in kd order with w = slot
 pclhip_status launch_normals_at(pclhip_index* ix, const float4* queries, uint32_t nq, int k, double radius, const float vp[3],

@@ -362,7 +362,12 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
   const float4* q = self ? ix->pts : queries;
   float4* dst = self ? ix->nrm : out;
   if (n == 0) {
-    if (self) ix->has_normals = true;
+    if (self) {
+      const pclhip_status sp = launch_plane_records(ix);  // all pads
+      if (sp != PCLHIP_OK) return sp;
+      PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+      ix->has_normals = true;
+    }
     return PCLHIP_OK;
   }
   // few queries on a large surface: fewer of them per wavefront (api.hip: sparse_layout).  The padding slots write their NaN
@@ -403,6 +408,10 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
                        d_nan);
   (void)hipEventRecord(e1, s);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+  if (self) {
+    const pclhip_status sp = launch_plane_records(ix);
+    if (sp != PCLHIP_OK) return sp;
+  }
   unsigned long long h = 0;
   if (dst != out && !self) PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(out, dst, size_t(nq) * sizeof(float4), hipMemcpyDeviceToDevice, s));
   PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&h, d_nan, 8, hipMemcpyDeviceToHost, s));

@@ -542,6 +542,35 @@ __global__ void iota_w_kernel(const float4* __restrict__ pts, uint32_t n, float4
   }
 }
 
+// transformation_estimation_point_to_plane_lls.hpp:235: the residual nx*dx + ny*dy + nz*dz - nx*sx - ny*sy - nz*sz is
+// evaluated in float, left to right; this is its first half, which depends on the target point t and its normal n alone
+__device__ __forceinline__ float plane_prefix(const float4 n, const float4 t) {
+  float c = __fmul_rn(n.x, t.x);
+  c = __fadd_rn(c, __fmul_rn(n.y, t.y));
+  return __fadd_rn(c, __fmul_rn(n.z, t.z));
+}
+
+// The point-to-plane residual (PairAcc<1>::add) starts with the float prefix n.t of the TARGET point alone: computed here
+// once per point, in the same order with the same roundings, so the accumulation gathers one 16-byte record per pair.
+// Pads and points without a normal carry NaN normals (the prefix is then NaN too): the pair is skipped either way.
+__global__ void plane_records_kernel(const float4* __restrict__ pts, const float4* __restrict__ nrm, uint32_t n_pad,
+                                     float4* __restrict__ plane) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pad) return;
+  const float4 t = pts[i], n = nrm[i];
+  plane[i] = make_float4(n.x, n.y, n.z, plane_prefix(n, t));
+}
+
+pclhip_status launch_plane_records(pclhip_index* ix) {
+  pclhip_ctx* ctx = ix->ctx;
+  if (!ix->plane) PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &ix->plane, size_t(ix->n_pad > 0 ? ix->n_pad : 1) * sizeof(float4)));
+  if (ix->n_pad == 0) return PCLHIP_OK;
+  hipLaunchKernelGGL(plane_records_kernel, dim3((ix->n_pad + 255) / 256), dim3(256), 0, ctx->stream, ix->pts, ix->nrm, ix->n_pad,
+                     ix->plane);
+  PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+  return PCLHIP_OK;
+}
+
 pclhip_status launch_normals(pclhip_index* ix, int k, const float vp[3], uint64_t* nan_count) {
   pclhip_ctx* ctx = ix->ctx;
   hipStream_t s = ctx->stream;
@@ -594,6 +623,9 @@ pclhip_status launch_normals(pclhip_index* ix, int k, const float vp[3], uint64_
   float ms = 0;
   if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ix->last_kernel_ms = ms;
   if (nan_count) *nan_count = h;
+  const pclhip_status sp = launch_plane_records(ix);
+  if (sp != PCLHIP_OK) return sp;
+  PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
   ix->has_normals = true;
   return PCLHIP_OK;
 }
@@ -1566,41 +1598,50 @@ struct PairAcc {
     cnt = 0;
     skipped = 0;
   }
+  // MODE 1 from a plane record (nx, ny, nz, plane_prefix(n, t)) of the matched target point: the same terms, bit for bit
+  __device__ __forceinline__ void add_plane(const float4 p, const float4 n, float d2) {
+    static_assert(MODE == PCLHIP_ICP_POINT_TO_PLANE, "plane records serve the point-to-plane objective");
+    ++cnt;
+    sum_d2 += double(d2);
+    if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
+      const float sx = p.x, sy = p.y, sz = p.z;
+      const float nx = n.x, ny = n.y, nz = n.z;
+      const double a = double(__fsub_rn(__fmul_rn(nz, sy), __fmul_rn(ny, sz)));
+      const double b = double(__fsub_rn(__fmul_rn(nx, sz), __fmul_rn(nz, sx)));
+      const double c = double(__fsub_rn(__fmul_rn(ny, sx), __fmul_rn(nx, sy)));
+      acc[0] += a * a;  acc[1] += a * b;  acc[2] += a * c;
+      acc[3] += a * double(nx); acc[4] += a * double(ny); acc[5] += a * double(nz);
+      acc[6] += b * b;  acc[7] += b * c;
+      acc[8] += b * double(nx); acc[9] += b * double(ny); acc[10] += b * double(nz);
+      acc[11] += c * c;
+      acc[12] += c * double(nx); acc[13] += c * double(ny); acc[14] += c * double(nz);
+      acc[15] += double(__fmul_rn(nx, nx)); acc[16] += double(__fmul_rn(nx, ny));
+      acc[17] += double(__fmul_rn(nx, nz)); acc[18] += double(__fmul_rn(ny, ny));
+      acc[19] += double(__fmul_rn(ny, nz)); acc[20] += double(__fmul_rn(nz, nz));
+      // :235  nx*dx + ny*dy + nz*dz - nx*sx - ny*sy - nz*sz, float, left to right (plane_prefix: the first three terms)
+      float df = __fsub_rn(n.w, __fmul_rn(nx, sx));
+      df = __fsub_rn(df, __fmul_rn(ny, sy));
+      df = __fsub_rn(df, __fmul_rn(nz, sz));
+      const double d = double(df);
+      acc[21] += a * d; acc[22] += b * d; acc[23] += c * d;
+      acc[24] += double(nx) * d; acc[25] += double(ny) * d; acc[26] += double(nz) * d;
+    } else {
+      ++skipped;
+    }
+  }
+  // MODE 0 / 1 from what target_record() gathers: the target point, or its plane record
+  __device__ __forceinline__ void add_record(const float4 p, const float4 rec, float d2) {
+    if constexpr (MODE == PCLHIP_ICP_POINT_TO_PLANE) add_plane(p, rec, d2);
+    else add(p, make_float4(0, 0, 0, 0), rec, make_float4(0, 0, 0, 0), d2, false);
+  }
   // p: source point (already moved), n1: its normal (MODE 2), t: matched target point, n: its normal
   __device__ __forceinline__ void add(const float4 p, const float4 n1, const float4 t, const float4 n, float d2,
                                       bool enforce_same_direction) {
-    ++cnt;
-    sum_d2 += double(d2);
     if constexpr (MODE == PCLHIP_ICP_POINT_TO_PLANE) {
-      if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
-        const float sx = p.x, sy = p.y, sz = p.z;
-        const float nx = n.x, ny = n.y, nz = n.z;
-        const double a = double(__fsub_rn(__fmul_rn(nz, sy), __fmul_rn(ny, sz)));
-        const double b = double(__fsub_rn(__fmul_rn(nx, sz), __fmul_rn(nz, sx)));
-        const double c = double(__fsub_rn(__fmul_rn(ny, sx), __fmul_rn(nx, sy)));
-        acc[0] += a * a;  acc[1] += a * b;  acc[2] += a * c;
-        acc[3] += a * double(nx); acc[4] += a * double(ny); acc[5] += a * double(nz);
-        acc[6] += b * b;  acc[7] += b * c;
-        acc[8] += b * double(nx); acc[9] += b * double(ny); acc[10] += b * double(nz);
-        acc[11] += c * c;
-        acc[12] += c * double(nx); acc[13] += c * double(ny); acc[14] += c * double(nz);
-        acc[15] += double(__fmul_rn(nx, nx)); acc[16] += double(__fmul_rn(nx, ny));
-        acc[17] += double(__fmul_rn(nx, nz)); acc[18] += double(__fmul_rn(ny, ny));
-        acc[19] += double(__fmul_rn(ny, nz)); acc[20] += double(__fmul_rn(nz, nz));
-        // :235  nx*dx + ny*dy + nz*dz - nx*sx - ny*sy - nz*sz, float, left to right
-        float df = __fmul_rn(nx, t.x);
-        df = __fadd_rn(df, __fmul_rn(ny, t.y));
-        df = __fadd_rn(df, __fmul_rn(nz, t.z));
-        df = __fsub_rn(df, __fmul_rn(nx, sx));
-        df = __fsub_rn(df, __fmul_rn(ny, sy));
-        df = __fsub_rn(df, __fmul_rn(nz, sz));
-        const double d = double(df);
-        acc[21] += a * d; acc[22] += b * d; acc[23] += c * d;
-        acc[24] += double(nx) * d; acc[25] += double(ny) * d; acc[26] += double(nz) * d;
-      } else {
-        ++skipped;
-      }
+      add_plane(p, make_float4(n.x, n.y, n.z, plane_prefix(n, t)), d2);
     } else if constexpr (MODE == PCLHIP_ICP_SYMMETRIC) {
+      ++cnt;
+      sum_d2 += double(d2);
       float nx, ny, nz;
       const float dot12 = __fadd_rn(__fadd_rn(__fmul_rn(n1.x, n.x), __fmul_rn(n1.y, n.y)), __fmul_rn(n1.z, n.z));
       if (enforce_same_direction && !(dot12 >= 0.0f)) {  // :169-174
@@ -1631,6 +1672,8 @@ struct PairAcc {
         ++skipped;
       }
     } else {
+      ++cnt;
+      sum_d2 += double(d2);
       const double sx = p.x, sy = p.y, sz = p.z, tx = t.x, ty = t.y, tz = t.z;
       acc[0] += sx; acc[1] += sy; acc[2] += sz;
       acc[3] += tx; acc[4] += ty; acc[5] += tz;
@@ -1670,6 +1713,15 @@ __device__ __forceinline__ float rotate_row(float r0, float r1, float r2, float 
   return __fadd_rn(__fmul_rn(r0, a), __fadd_rn(__fmul_rn(r1, b), __fmul_rn(r2, c)));
 }
 
+// What the accumulation gathers of a matched target point: the point (MODE 0) or its plane record (MODE 1,
+// PairAcc::add_record)
+template <int MODE>
+__device__ __forceinline__ float4 target_record(const IndexView& ix, uint32_t pos) {
+  static_assert(MODE != PCLHIP_ICP_SYMMETRIC, "the symmetric objective needs the target point and its normal");
+  if constexpr (MODE == PCLHIP_ICP_POINT_TO_PLANE) return ix.plane[pos];
+  else return ix.pts[pos];
+}
+
 template <int MODE>
 __global__ __launch_bounds__(BLOCK) void icp_accumulate_kernel(IndexView ix, const float4* __restrict__ cur, uint32_t ns,
                                                                const uint32_t* __restrict__ match_pos,
@@ -1695,31 +1747,30 @@ __global__ __launch_bounds__(BLOCK) void icp_accumulate_kernel(IndexView ix, con
 #define PCLHIP_ACC_PAIRS 2  // A/B: 1 = one pair per trip
 #endif
   if constexpr (MODE != PCLHIP_ICP_SYMMETRIC && PCLHIP_ACC_PAIRS == 2) {
-    // Two pairs per trip: both match positions, then both gathers of (target point, normal), are in flight together --
-    // the kernel is a chain of two dependent memory levels per pair and nothing else (113 -> 111 us at 10M pairs).
+    // Two pairs per trip: both match positions, then both gathers of the target record, are in flight together -- the
+    // kernel is a chain of two dependent memory levels per pair and nothing else (113 -> 111 us at 10M pairs).  The
+    // record is the target point (MODE 0) or its plane record (MODE 1: one 16-byte gather instead of point + normal).
     // Pairs are still added in the order i, i + step, ...: the sums are the same, bit for bit.
     for (; uint64_t(i) + step < ns; i += 2u * step) {
       const uint32_t ia = i, ib = i + step;
       const uint32_t pos_a = match_pos[ia], pos_b = match_pos[ib];
       const bool ok_a = pos_a != NO_INDEX && (keep == nullptr || keep[ia]);
       const bool ok_b = pos_b != NO_INDEX && (keep == nullptr || keep[ib]);
-      float4 pa4 = make_float4(0, 0, 0, 0), ta = pa4, na = pa4, pb4 = pa4, tb = pa4, nb = pa4;
+      const float4 zero = make_float4(0, 0, 0, 0);
+      float4 pa4 = zero, ta = zero, pb4 = zero, tb = zero;
       float da = 0.0f, db = 0.0f;
       if (ok_a) {
         pa4 = cur[ia];
-        ta = ix.pts[pos_a];
-        if constexpr (MODE != PCLHIP_ICP_POINT_TO_POINT) na = ix.nrm[pos_a];
+        ta = target_record<MODE>(ix, pos_a);
         da = match_d2[ia];
       }
       if (ok_b) {
         pb4 = cur[ib];
-        tb = ix.pts[pos_b];
-        if constexpr (MODE != PCLHIP_ICP_POINT_TO_POINT) nb = ix.nrm[pos_b];
+        tb = target_record<MODE>(ix, pos_b);
         db = match_d2[ib];
       }
-      const float4 zero = make_float4(0, 0, 0, 0);
-      if (ok_a) pa.add(pa4, zero, ta, na, da, enforce != 0);
-      if (ok_b) pa.add(pb4, zero, tb, nb, db, enforce != 0);
+      if (ok_a) pa.add_record(pa4, ta, da);
+      if (ok_b) pa.add_record(pb4, tb, db);
     }
   }
   for (; i < ns; i += step) {
@@ -1738,10 +1789,11 @@ __global__ __launch_bounds__(BLOCK) void icp_accumulate_kernel(IndexView ix, con
     if (pos == NO_INDEX) continue;
     if (keep != nullptr && !keep[i]) continue;  // rejected by the reciprocal test / rejector chain
     const float4 p = cur[i];
-    const float4 t = ix.pts[pos];
-    float4 n = make_float4(0, 0, 0, 0);
-    if constexpr (MODE != PCLHIP_ICP_POINT_TO_POINT) n = ix.nrm[pos];
-    pa.add(p, n1, t, n, match_d2[i], enforce != 0);
+    if constexpr (MODE == PCLHIP_ICP_SYMMETRIC) {
+      pa.add(p, n1, ix.pts[pos], ix.nrm[pos], match_d2[i], enforce != 0);
+    } else {
+      pa.add_record(p, target_record<MODE>(ix, pos), match_d2[i]);
+    }
   }
   pa.store_block(red_s, partials);
 }
@@ -1761,18 +1813,13 @@ __global__ __launch_bounds__(BLOCK) void icp_accumulate_owned_kernel(IndexView i
   PairAcc<MODE> pa;
   pa.init();
   const uint64_t slots = uint64_t(og.count[0]) * WAVE;
-  const float4 zero = make_float4(0, 0, 0, 0);
   for (uint64_t s = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; s < slots; s += uint64_t(gridDim.x) * blockDim.x) {
     const uint32_t i = og.list[s / WAVE] * WAVE + uint32_t(s % WAVE);
     if (i >= ns) continue;
     const uint32_t pos = match_pos[i];
     if (pos == NO_INDEX) continue;
     if (keep != nullptr && !keep[i]) continue;
-    const float4 p = cur[i];
-    const float4 t = ix.pts[pos];
-    float4 n = zero;
-    if constexpr (MODE != PCLHIP_ICP_POINT_TO_POINT) n = ix.nrm[pos];
-    pa.add(p, zero, t, n, match_d2[i], enforce != 0);
+    pa.add_record(cur[i], target_record<MODE>(ix, pos), match_d2[i]);
   }
   pa.store_block(red_s, partials);
 }
