@@ -228,6 +228,45 @@ PCLHIP_API pclhip_status pclhip_normals_at(pclhip_index* surface, const void* qu
  * 20, <= 32 here), regularised to singular values (1, 1, epsilon) (gicp_epsilon_, default 0.001).
  * out (host or device): 9 doubles (row-major 3x3) per ORIGINAL cloud point; NaN for dropped points. */
 PCLHIP_API pclhip_status pclhip_gicp_covariances(pclhip_index* index, int k, double epsilon, double* out);
+
+/* ---- outlier removal over an index built over the WHOLE input cloud (no indices, unscaled) ----------
+ * Queries: every record of the cloud (indices == NULL) or indices[0..n_indices) in that order, each against the whole
+ * index; kept / removed (host or device, each room for as many ids as there are queries, either may be NULL) receive
+ * the queries' record ids in query order (FilterIndices::filter(Indices&), filters/include/pcl/filters/impl/
+ * filter_indices.hpp:77-107; getRemovedIndices).  A record the index dropped (non-finite) has no neighbours.  Organized
+ * clouds are searched with the same exact index where the reference would pick OrganizedNeighbor.
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call. */
+typedef struct pclhip_sor_stats {
+  double mean;       /* of the valid (finite) queries' mean distances */
+  double stddev;
+  double threshold;  /* mean + std_mul * stddev */
+  double sum;        /* sum of the distances (non-finite queries add 0) */
+  double sq_sum;     /* sum of fl(d * d) */
+  uint64_t valid;    /* finite queries */
+} pclhip_sor_stats;
+/* pcl::StatisticalOutlierRemoval<PointT>::applyFilterIndices (filters/include/pcl/filters/impl/
+ * statistical_outlier_removal.hpp:47-132).  Per query the mean of sqrt(d2) over its neighbours 1..K-1, K =
+ * min(mean_k + 1, finite points) (the query itself is neighbour 0): the square root is taken in double of the float d2,
+ * summed in ascending order in double, divided by K - 1 and rounded to float, as :96-99.  Non-finite queries get 0 and
+ * are not counted in `valid`.  The statistics (:104-117) are sums in double over a fixed-order tree -- bitwise
+ * repeatable, but not the reference's sequential sum (agreement to ~1e-15 relative).  A query is removed iff d >
+ * threshold (negative: d <= threshold); a NaN distance or threshold removes nothing.  mean_distances (host or device,
+ * optional): the per-query mean distances; stats (optional).  mean_k < 1 is PCLHIP_ERR_INVALID (the reference divides
+ * by zero). */
+PCLHIP_API pclhip_status pclhip_statistical_outlier_removal(pclhip_index* index, const int32_t* indices, uint64_t n_indices,
+                                                            int mean_k, double std_mul, int negative, int32_t* kept,
+                                                            uint64_t* n_kept, int32_t* removed, uint64_t* n_removed,
+                                                            float* mean_distances, pclhip_sor_stats* stats);
+/* pcl::RadiusOutlierRemoval<PointT>::applyFilterIndices (filters/include/pcl/filters/impl/radius_outlier_removal.hpp
+ * :48-172).  A query has enough neighbours when at least min_pts + 1 points of the index (itself included) lie within
+ * the radius; "within" is (double)d2 <= r*r for is_dense (the nearestKSearch path, :84-115) and d2 < float(r*r)
+ * otherwise (the radiusSearch path, :119-147, as pclhip_radius_search).  is_dense: kept iff enough XOR negative;
+ * otherwise a non-finite query is always removed and a finite one kept iff enough XOR negative.  radius == 0 is
+ * PCLHIP_ERR_INVALID (:52-58). */
+PCLHIP_API pclhip_status pclhip_radius_outlier_removal(pclhip_index* index, const int32_t* indices, uint64_t n_indices,
+                                                       double radius, int min_pts, int is_dense, int negative,
+                                                       int32_t* kept, uint64_t* n_kept, int32_t* removed,
+                                                       uint64_t* n_removed);
 /* GPU time (ms) of the last pclhip_knn / pclhip_normals traversal kernel on this index. */
 PCLHIP_API double pclhip_index_last_kernel_ms(const pclhip_index* index);
 /* Supply target normals computed elsewhere (e.g. a pcl::PointNormal target: normals = points + 16,

@@ -1462,4 +1462,138 @@ class VoxelGrid {
   double lo_ = -FLT_MAX, hi_ = FLT_MAX;
 };
 
+
+// ---- outlier removal: FilterIndices<PointT> (filters/include/pcl/filters/filter_indices.h, impl/filter_indices.hpp:77-107)
+// over pclhip_statistical_outlier_removal / pclhip_radius_outlier_removal.  Every filter call indexes the input cloud (the
+// whole cloud: setIndices selects the queries, as in the reference, not the searched points).
+template <typename PointT>
+class OutlierRemovalBase : public PCLBase<PointT> {
+ public:
+  explicit OutlierRemovalBase(Context::Ptr ctx, bool extract_removed_indices)
+      : ctx_(std::move(ctx)), extract_removed_indices_(extract_removed_indices) {}
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  void setKeepOrganized(bool keep) { keep_organized_ = keep; }
+  bool getKeepOrganized() const { return keep_organized_; }
+  void setUserFilterValue(float value) { user_filter_value_ = value; }
+  void setNumberOfThreads(unsigned) {}  // accepted: the GPU decides its own parallelism
+  IndicesConstPtr getRemovedIndices() const { return removed_indices_; }
+  const std::string& getLastError() const { return error_; }
+  // filter(Indices&): the kept ids in input (or setIndices) order
+  void filter(Indices& indices) {
+    indices.clear();
+    removed_indices_ = std::make_shared<Indices>();
+    if (!this->input_ || !ctx_ || !ctx_->ok()) return;
+    const PointCloud<PointT>& in = *this->input_;
+    pclhip_index* ix = nullptr;
+    if (pclhip_index_build(ctx_->get(), in.points.data(), sizeof(PointT), in.size(), nullptr, 0, &ix) != PCLHIP_OK) {
+      error_ = pclhip_last_error(ctx_->get());
+      return;
+    }
+    const bool all = !this->indices_ || this->fake_indices_;
+    const std::size_t m = all ? in.size() : this->indices_->size();
+    Indices kept(m), removed(m);
+    std::uint64_t nk = 0, nr = 0;
+    const pclhip_status st = run(ix, all ? nullptr : this->indices_->data(), m, in.is_dense, kept.data(), &nk,
+                                 (extract_removed_indices_ || keep_organized_) ? removed.data() : nullptr, &nr);
+    if (st != PCLHIP_OK) error_ = pclhip_last_error(ctx_->get());
+    pclhip_index_destroy(ix);
+    if (st != PCLHIP_OK) return;
+    kept.resize(std::size_t(nk));
+    indices.swap(kept);
+    if (extract_removed_indices_ || keep_organized_) {
+      removed.resize(std::size_t(nr));
+      removed_indices_ = std::make_shared<Indices>(std::move(removed));
+    }
+  }
+  // filter(PointCloud&): copyPointCloud of the kept points (width = kept, height 1, is_dense of the input); with
+  // setKeepOrganized the input with the xyz of removed points set to the user filter value
+  void filter(PointCloud<PointT>& output) {
+    if (keep_organized_) extract_removed_indices_ = true;  // filter_indices.hpp:82-86
+    Indices kept;
+    filter(kept);
+    if (!this->input_) {
+      output = PointCloud<PointT>();
+      output.width = 0;
+      return;
+    }
+    const PointCloud<PointT>& in = *this->input_;
+    if (keep_organized_) {
+      output = in;
+      for (const index_t r : *removed_indices_) {
+        output.points[std::size_t(r)].x = user_filter_value_;
+        output.points[std::size_t(r)].y = user_filter_value_;
+        output.points[std::size_t(r)].z = user_filter_value_;
+      }
+      if (!std::isfinite(user_filter_value_)) output.is_dense = false;
+      return;
+    }
+    PointCloud<PointT> out;
+    out.points.reserve(kept.size());
+    for (const index_t i : kept) out.points.push_back(in.points[std::size_t(i)]);
+    out.width = std::uint32_t(kept.size());
+    out.height = 1;
+    out.is_dense = in.is_dense;
+    output = std::move(out);
+  }
+
+ protected:
+  virtual pclhip_status run(pclhip_index* ix, const index_t* idx, std::size_t m, bool dense, index_t* kept,
+                            std::uint64_t* nk, index_t* removed, std::uint64_t* nr) = 0;
+  Context::Ptr ctx_;
+  bool extract_removed_indices_ = false, negative_ = false, keep_organized_ = false;
+  float user_filter_value_ = std::numeric_limits<float>::quiet_NaN();
+  IndicesPtr removed_indices_ = std::make_shared<Indices>();
+  std::string error_;
+};
+
+// filters/include/pcl/filters/statistical_outlier_removal.h, impl/statistical_outlier_removal.hpp:47-132
+template <typename PointT>
+class StatisticalOutlierRemoval : public OutlierRemovalBase<PointT> {
+ public:
+  explicit StatisticalOutlierRemoval(bool extract_removed_indices = false)
+      : StatisticalOutlierRemoval(Context::defaultContext(), extract_removed_indices) {}
+  StatisticalOutlierRemoval(Context::Ptr ctx, bool extract_removed_indices)
+      : OutlierRemovalBase<PointT>(std::move(ctx), extract_removed_indices) {}
+  void setMeanK(int k) { mean_k_ = k; }
+  int getMeanK() const { return mean_k_; }
+  void setStddevMulThresh(double m) { std_mul_ = m; }
+  double getStddevMulThresh() const { return std_mul_; }
+  const pclhip_sor_stats& lastStatistics() const { return stats_; }
+
+ protected:
+  pclhip_status run(pclhip_index* ix, const index_t* idx, std::size_t m, bool, index_t* kept, std::uint64_t* nk,
+                    index_t* removed, std::uint64_t* nr) override {
+    return pclhip_statistical_outlier_removal(ix, idx, m, mean_k_, std_mul_, this->negative_ ? 1 : 0, kept, nk, removed, nr,
+                                              nullptr, &stats_);
+  }
+  int mean_k_ = 1;
+  double std_mul_ = 0.0;
+  pclhip_sor_stats stats_{};
+};
+
+// filters/include/pcl/filters/radius_outlier_removal.h, impl/radius_outlier_removal.hpp:48-172 (the cloud's is_dense
+// picks the boundary of "within")
+template <typename PointT>
+class RadiusOutlierRemoval : public OutlierRemovalBase<PointT> {
+ public:
+  explicit RadiusOutlierRemoval(bool extract_removed_indices = false)
+      : RadiusOutlierRemoval(Context::defaultContext(), extract_removed_indices) {}
+  RadiusOutlierRemoval(Context::Ptr ctx, bool extract_removed_indices)
+      : OutlierRemovalBase<PointT>(std::move(ctx), extract_removed_indices) {}
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setMinNeighborsInRadius(int n) { min_pts_ = n; }
+  int getMinNeighborsInRadius() const { return min_pts_; }
+
+ protected:
+  pclhip_status run(pclhip_index* ix, const index_t* idx, std::size_t m, bool dense, index_t* kept, std::uint64_t* nk,
+                    index_t* removed, std::uint64_t* nr) override {
+    return pclhip_radius_outlier_removal(ix, idx, m, radius_, min_pts_, dense ? 1 : 0, this->negative_ ? 1 : 0, kept, nk,
+                                         removed, nr);
+  }
+  double radius_ = 0.0;
+  int min_pts_ = 1;
+};
+
 }  // namespace pclhip

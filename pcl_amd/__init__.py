@@ -8,5 +8,6 @@ from .api import (Communicator, Context, CorrespondenceEstimation, Correspondenc
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, GeneralizedIterativeClosestPoint,
                   IterativeClosestPoint,
-                  IterativeClosestPointWithNormals, KdTree, NormalEstimation, VoxelGrid,
+                  IterativeClosestPointWithNormals, KdTree, NormalEstimation, RadiusOutlierRemoval,
+                  StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

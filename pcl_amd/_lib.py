@@ -82,6 +82,11 @@ class VoxelGridDims(C.Structure):
     _fields_ = [("min_b", C.c_int32 * 3), ("max_b", C.c_int32 * 3), ("div_b", C.c_int32 * 3), ("divb_mul", C.c_int32 * 3)]
 
 
+class SorStats(C.Structure):
+    _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("sum", C.c_double),
+                ("sq_sum", C.c_double), ("valid", C.c_uint64)]
+
+
 COMM_ID_BYTES = 128
 
 
@@ -167,6 +172,10 @@ SIGNATURES = {
     "pclhip_icp_last_search_ms": (C.c_double, [_vp]),
     "pclhip_icp_source_order_ms": (C.c_double, [_vp]),
     "pclhip_index_last_kernel_ms": (C.c_double, [_vp]),
+    "pclhip_statistical_outlier_removal": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_double, C.c_int, _vp,
+                                                     C.POINTER(_u64), _vp, C.POINTER(_u64), _vp, C.POINTER(SorStats)]),
+    "pclhip_radius_outlier_removal": (C.c_int, [_vp, _vp, _u64, C.c_double, C.c_int, C.c_int, C.c_int, _vp,
+                                                C.POINTER(_u64), _vp, C.POINTER(_u64)]),
     "pclhip_solve_transformation": (C.c_int, [C.POINTER(C.c_double), C.c_int,
                                               C.POINTER(C.c_float)]),
     "pclhip_icp_align": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(C.c_float),

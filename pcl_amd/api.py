@@ -1499,3 +1499,236 @@ class VoxelGrid:
 
     def getCentroidIndex(self, p):
         return self.getCentroidIndexAt(self.getGridCoordinates(p[0], p[1], p[2]))
+
+
+class _OutlierRemoval:
+    """FilterIndices<PointT> surface shared by StatisticalOutlierRemoval and RadiusOutlierRemoval
+    (filters/include/pcl/filters/filter_indices.h, impl/filter_indices.hpp:77-107).  The input is an (n, c >= 3) float32
+    cloud, numpy or a torch CUDA tensor; results come back in the same kind of array."""
+
+    def __init__(self, ctx=None, extract_removed_indices=False):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.extract_removed_indices = bool(extract_removed_indices)
+        self._cloud = None
+        self._is_dense = None
+        self._indices = None
+        self._negative = False
+        self._keep_organized = False
+        self._user_value = float("nan")
+        self._tree = None      # setSearchMethod
+        self._own = None       # the index this filter built, cached for the same cloud object
+        self._own_key = None
+        self._removed = np.empty(0, np.int32)
+        self._ms = 0.0
+        self._threads = 0
+
+    def getClassName(self):
+        return type(self).__name__
+
+    def setInputCloud(self, cloud, is_dense=None):
+        """is_dense: the PointCloud's flag; None = every point is finite (computed)."""
+        self._cloud = cloud
+        self._is_dense = None if is_dense is None else bool(is_dense)
+
+    def getInputCloud(self):
+        return self._cloud
+
+    def setIndices(self, indices):
+        self._indices = indices
+
+    def getIndices(self):
+        return self._indices
+
+    def setNegative(self, negative):
+        self._negative = bool(negative)
+
+    def getNegative(self):
+        return self._negative
+
+    def setKeepOrganized(self, keep):
+        self._keep_organized = bool(keep)
+
+    def getKeepOrganized(self):
+        return self._keep_organized
+
+    def setUserFilterValue(self, value):
+        self._user_value = float(value)
+
+    def setNumberOfThreads(self, n):
+        """Accepted for PCL compatibility; the GPU decides its own parallelism."""
+        self._threads = int(n)
+
+    def setSearchMethod(self, tree):
+        """A KdTree already built over this filter's (unscaled, whole) input cloud is reused; any other tree is ignored and
+        the filter builds its own index."""
+        self._tree = tree
+
+    def getSearchMethod(self):
+        return self._tree
+
+    def getRemovedIndices(self):
+        return self._removed
+
+    def lastKernelMs(self):
+        """GPU time of the last filter call (all of its kernels)."""
+        return self._ms
+
+    def _dense(self):
+        if self._is_dense is not None:
+            return self._is_dense
+        c = self._cloud
+        if _is_torch(c):
+            import torch
+            return bool(torch.isfinite(c[:, :3]).all().item())
+        return bool(np.isfinite(np.asarray(c, np.float32)[:, :3]).all())
+
+    def _index(self):
+        t = self._tree
+        if (t is not None and getattr(t, "h", None) and t.getInputCloud() is self._cloud and t.getIndices() is None
+                and getattr(t, "_scale", None) is None):
+            return t.h
+        key = id(self._cloud)
+        if self._own is None or self._own_key != key or self._own._cloud is not self._cloud:
+            self._own = KdTree(self.ctx)
+            self._own.setInputCloud(self._cloud)
+            self._own_key = key
+        return self._own.h
+
+    def _run(self, call):
+        """call(index, idx_ptr, n_idx, kept_ptr, n_kept, removed_ptr, n_removed) -> (kept, removed) as arrays."""
+        assert self._cloud is not None, "setInputCloud first"
+        ptr, stride, n, keep = _cloud(self._cloud)
+        dev = _is_torch(self._cloud)
+        ind = self._indices
+        if ind is None:
+            m = n
+            iptr = None
+        elif _is_torch(ind):
+            ind = ind.to(dtype=__import__("torch").int32).contiguous()
+            m = int(ind.numel())
+            iptr = C.c_void_p(ind.data_ptr())
+        else:
+            ind = np.ascontiguousarray(ind, np.int32)
+            m = len(ind)
+            iptr = C.c_void_p(ind.ctypes.data)
+        want_removed = self.extract_removed_indices or self._keep_organized
+        if dev:
+            import torch
+            kept = torch.empty(max(m, 1), dtype=torch.int32, device=self._cloud.device)
+            rem = torch.empty(max(m, 1), dtype=torch.int32, device=self._cloud.device) if want_removed else None
+            kp, rp = C.c_void_p(kept.data_ptr()), (C.c_void_p(rem.data_ptr()) if rem is not None else None)
+        else:
+            kept = np.empty(max(m, 1), np.int32)
+            rem = np.empty(max(m, 1), np.int32) if want_removed else None
+            kp, rp = C.c_void_p(kept.ctypes.data), (C.c_void_p(rem.ctypes.data) if rem is not None else None)
+        nk, nr = C.c_uint64(0), C.c_uint64(0)
+        h = self._index()
+        check(call(h, iptr, m, kp, C.byref(nk), rp, C.byref(nr)), self.ctx.h)
+        self._ms = float(self.lib.pclhip_index_last_kernel_ms(h))
+        kept = kept[:nk.value]
+        if rem is not None:
+            rem = rem[:nr.value]
+        else:
+            rem = kept[:0]
+        self._removed = rem if self.extract_removed_indices or self._keep_organized else kept[:0]
+        return kept, rem
+
+    def filterIndices(self):
+        """filter(Indices&): the ids of the kept points, in input (or setIndices) order."""
+        kept, _ = self._run(self._call)
+        return kept
+
+    def filter(self):
+        """filter(PointCloud&): the kept records in the input's layout; with setKeepOrganized the whole input with the xyz of
+        removed records set to the user filter value."""
+        if self._keep_organized:
+            self.extract_removed_indices = True  # filter_indices.hpp:82-86
+        kept, rem = self._run(self._call)
+        c = self._cloud
+        if self._keep_organized:
+            if _is_torch(c):
+                out = c.clone()
+                out[rem.long(), :3] = self._user_value
+            else:
+                out = np.array(c, np.float32, copy=True)
+                out[rem, :3] = np.float32(self._user_value)
+            return out
+        if _is_torch(c):
+            return c.index_select(0, kept.long())
+        return np.asarray(c, np.float32)[kept]
+
+
+class StatisticalOutlierRemoval(_OutlierRemoval):
+    """pcl::StatisticalOutlierRemoval<PointT> (filters/include/pcl/filters/statistical_outlier_removal.h,
+    impl/statistical_outlier_removal.hpp:47-132) over pclhip_statistical_outlier_removal."""
+
+    def __init__(self, ctx=None, extract_removed_indices=False):
+        super().__init__(ctx, extract_removed_indices)
+        self._mean_k = 1
+        self._std_mul = 0.0
+        self._dist = None
+        self._stats = None
+
+    def setMeanK(self, k):
+        self._mean_k = int(k)
+
+    def getMeanK(self):
+        return self._mean_k
+
+    def setStddevMulThresh(self, m):
+        self._std_mul = float(m)
+
+    def getStddevMulThresh(self):
+        return self._std_mul
+
+    def lastMeanDistances(self):
+        """Per query (input or setIndices order) the mean distance to its mean_k neighbours (0 for non-finite points)."""
+        return self._dist
+
+    def lastStatistics(self):
+        """dict(mean, stddev, threshold, sum, sq_sum, valid) of the last call."""
+        return self._stats
+
+    def _call(self, h, iptr, m, kp, nk, rp, nr):
+        if _is_torch(self._cloud):
+            import torch
+            self._dist = torch.empty(max(m, 1), dtype=torch.float32, device=self._cloud.device)
+            dptr = C.c_void_p(self._dist.data_ptr())
+        else:
+            self._dist = np.empty(max(m, 1), np.float32)
+            dptr = C.c_void_p(self._dist.ctypes.data)
+        st = _lib.SorStats()
+        r = self.lib.pclhip_statistical_outlier_removal(h, iptr, m, self._mean_k, self._std_mul, int(self._negative), kp, nk,
+                                                        rp, nr, dptr, C.byref(st))
+        self._dist = self._dist[:m]
+        self._stats = dict(mean=st.mean, stddev=st.stddev, threshold=st.threshold, sum=st.sum, sq_sum=st.sq_sum,
+                           valid=int(st.valid))
+        return r
+
+
+class RadiusOutlierRemoval(_OutlierRemoval):
+    """pcl::RadiusOutlierRemoval<PointT> (filters/include/pcl/filters/radius_outlier_removal.h,
+    impl/radius_outlier_removal.hpp:48-172) over pclhip_radius_outlier_removal.  Which "within" boundary applies follows
+    the cloud's is_dense flag (setInputCloud)."""
+
+    def __init__(self, ctx=None, extract_removed_indices=False):
+        super().__init__(ctx, extract_removed_indices)
+        self._radius = 0.0
+        self._min_pts = 1
+
+    def setRadiusSearch(self, r):
+        self._radius = float(r)
+
+    def getRadiusSearch(self):
+        return self._radius
+
+    def setMinNeighborsInRadius(self, n):
+        self._min_pts = int(n)
+
+    def getMinNeighborsInRadius(self):
+        return self._min_pts
+
+    def _call(self, h, iptr, m, kp, nk, rp, nr):
+        return self.lib.pclhip_radius_outlier_removal(h, iptr, m, self._radius, self._min_pts, int(self._dense()),
+                                                      int(self._negative), kp, nk, rp, nr)

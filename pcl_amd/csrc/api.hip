@@ -1300,6 +1300,67 @@ pclhip_status pclhip_index_set_normals(pclhip_index* ix, const void* normals, si
   return PCLHIP_OK;
 }
 
+// ---- outlier removal (outlier.hpp) --------------------------------------------------------------
+pclhip_status pclhip_statistical_outlier_removal(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, int mean_k,
+                                                 double std_mul, int negative, int32_t* kept, uint64_t* n_kept,
+                                                 int32_t* removed, uint64_t* n_removed, float* mean_distances,
+                                                 pclhip_sor_stats* stats) {
+  if (!ix || !n_kept || !n_removed) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_kept = 0;
+  *n_removed = 0;
+  // statistical_outlier_removal.hpp:99 divides by mean_k_ (nn_dists.size() - 1): mean_k < 1 is refused here
+  PCLHIP_REQUIRE(ctx, mean_k >= 1, "mean_k must be >= 1");
+  PCLHIP_REQUIRE(ctx, !ix->scaled, "outlier removal searches the cloud's own coordinates: build the index unscaled");
+  OutlierParams prm;
+  prm.kind = OutlierParams::SOR;
+  prm.mean_k = mean_k;
+  prm.std_mul = std_mul;
+  prm.negative = negative != 0;
+  double st6[6];
+  const pclhip_status st = outlier_filter(ix, indices, n_indices, prm, kept, n_kept, removed, n_removed, mean_distances, st6);
+  if (st == PCLHIP_OK && stats) {
+    stats->mean = st6[0];
+    stats->stddev = st6[1];
+    stats->threshold = st6[2];
+    stats->sum = st6[3];
+    stats->sq_sum = st6[4];
+    stats->valid = uint64_t(st6[5]);
+  }
+  return st;
+}
+
+pclhip_status pclhip_radius_outlier_removal(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius,
+                                            int min_pts, int is_dense, int negative, int32_t* kept, uint64_t* n_kept,
+                                            int32_t* removed, uint64_t* n_removed) {
+  if (!ix || !n_kept || !n_removed) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_kept = 0;
+  *n_removed = 0;
+  PCLHIP_REQUIRE(ctx, radius != 0.0, "no radius defined");  // radius_outlier_removal.hpp:52-58
+  PCLHIP_REQUIRE(ctx, min_pts >= 0, "min_pts must be >= 0");
+  PCLHIP_REQUIRE(ctx, !ix->scaled, "outlier removal searches the cloud's own coordinates: build the index unscaled");
+  // "within" as one float bound d2 <= t: dense clouds go through nearestKSearch and compare (double)d2 <= r*r
+  // (radius_outlier_removal.hpp:71,95-101): t = the largest float not above r*r; otherwise radiusSearch keeps d2 <
+  // float(r*r) (kdtree_flann.hpp:398, FLANN's RadiusResultSet): t = the float just below it
+  const double r2 = radius * radius;
+  float t = float(r2);
+  if (is_dense) {
+    if (double(t) > r2) t = std::nextafter(t, -INFINITY);
+  } else {
+    t = std::nextafter(t, -INFINITY);
+  }
+  OutlierParams prm;
+  prm.kind = OutlierParams::ROR;
+  prm.t = t;
+  prm.need = uint32_t(min_pts) + 1u;
+  prm.dense = is_dense != 0;
+  prm.negative = negative != 0;
+  return outlier_filter(ix, indices, n_indices, prm, kept, n_kept, removed, n_removed, nullptr, nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------
 void pclhip_icp_params_default(pclhip_icp_params* p) {
   if (!p) return;

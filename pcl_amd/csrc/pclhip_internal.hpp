@@ -507,6 +507,22 @@ pclhip_status sparse_layout(pclhip_ctx* ctx, const float4* q_sorted, uint64_t nq
 pclhip_status launch_knn(pclhip_index* ix, const float4* q_sorted, uint32_t nq, int k,
                          int32_t* out_idx_sorted, float* out_d2_sorted, bool timed = true);
 pclhip_status launch_normals(pclhip_index* ix, int k, const float vp[3], uint64_t* nan_count);
+// StatisticalOutlierRemoval / RadiusOutlierRemoval over the index (outlier.hpp, compiled into radius.hip).  SOR: mean_k,
+// std_mul; ROR: a record has enough neighbours when `need` points of the index lie within d2 <= t.  stats6 (SOR, optional):
+// mean, stddev, threshold, sum, sq_sum, valid.
+struct OutlierParams {
+  enum Kind { SOR = 0, ROR = 1 };
+  int kind = SOR;
+  int mean_k = 0;
+  double std_mul = 0.0;
+  float t = 0.0f;
+  uint32_t need = 0;
+  int dense = 1;
+  int negative = 0;
+};
+pclhip_status outlier_filter(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, const OutlierParams& prm,
+                             int32_t* kept, uint64_t* n_kept, int32_t* removed, uint64_t* n_removed, float* mean_dist,
+                             double* stats6);
 pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d2, bool use_max,
                                  int mode, hipEvent_t* step_events = nullptr);
 // target sharding, after a run of the device-driven loop: the working copies of the groups the last launches did not

@@ -424,3 +424,6 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
   if (self) ix->has_normals = true;
   return PCLHIP_OK;
 }
+
+// StatisticalOutlierRemoval / RadiusOutlierRemoval: their kernels traverse the same index (entry points in api.hip)
+#include "outlier.hpp"
