@@ -20,6 +20,11 @@ Target index + normals are built before the timed region (reported under "setup"
 Multi-GPU (weak scaling, configs 2/3): every rank holds the full target index and its own slab of the source;
 the only exchange per iteration is the all-reduce of the 32-double record (ncclAllReduce from C, RCCL/xGMI).
 
+A plain run does only what the headline needs: clouds, index and normals, the warm-up, the K timed steps, the
+--dump-outputs arrays, the JSON line.  --full adds the measurements that take runs of their own: the CPU baseline
+(configs 2-5), the host-boundary align() and the fresh frame (configs 2/3), the cloud families (config 3); their
+`cpu_baseline`, `setup.host_align`, `setup.fresh_frame` and `families` entries are null without it.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -66,10 +71,15 @@ def parse():
                     help="cloud family of configs 2/3 (pcl_amd/synth.py: family_cloud); the metric's config is the sheet")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="pclhip_ctx_set_option before anything is built (A/B runs: lane_search=0, lane_max_up=1, ...)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the CPU baseline, the "
+                         "host-boundary align(), the fresh frame and the cloud families")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-families", action="store_true",
-                    help="skip the `families` sub-record (the same measurement on the cube / layers / clusters clouds)")
-    ap.add_argument("--no-host-align", action="store_true", help="skip the host-boundary timing (examples/bench_pcl_align.cpp)")
+                    help="with --full: skip the `families` sub-record (the same measurement on the cube / layers / clusters "
+                         "clouds)")
+    ap.add_argument("--no-host-align", action="store_true",
+                    help="with --full: skip the host-boundary timing (examples/bench_pcl_align.cpp)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
                          "(float32 / float64, a fixed seeded sample of the larger arrays, at most 64 MB in all; configs 2-4)")
@@ -199,7 +209,7 @@ def main():
 
     # a fresh frame: a NEW source cloud against the resident target -- its ordering, then one whole alignment (device times)
     fresh_frame = None
-    if world == 1 and not args.rejectors and not args.reciprocal:
+    if args.full and world == 1 and not args.rejectors and not args.reciprocal:
         icp_f = cls(ctx)
         icp_f.setSearchMethodTarget(tree, True)
         icp_f.setInputSource(src)
@@ -265,8 +275,8 @@ def main():
     # (pcl_amd/synth.py: family_cloud; PCL's own search tests use volumetric random clouds, test/search/test_search.cpp
     # :292-364).  Not part of `value`: a sub-record, so that the driver's line shows how far the headline generalises.
     families = None
-    if (cfg == 3 and world == 1 and args.cloud == "sheet" and not args.no_families and not args.rejectors and not args.reciprocal
-            and not args.points):
+    if (args.full and cfg == 3 and world == 1 and args.cloud == "sheet" and not args.no_families and not args.rejectors
+            and not args.reciprocal and not args.points):
         families = {}
         sheet_ms = elapsed / max(args.steps, 1) * 1e3
         sheet_first = float(np.mean([s_["search_ms"] for s_ in steps if s_["iteration"] == 1] or [0.0]))
@@ -302,10 +312,10 @@ def main():
     out = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # an N=1 figure (it would stall the other ranks)
+        if args.full and not args.no_cpu_baseline and world == 1:  # an N=1 figure (it would stall the other ranks)
             cpu = cpu_baseline(args, mode, n, tgt_h, src_h)
         boundary = None
-        if not args.no_host_align and world == 1:
+        if args.full and not args.no_host_align and world == 1:
             boundary = host_align(mode, tgt_h, src_h)
         name = {2: "config 2: 2^20-point clouds, k=1 NN + point-to-point ICP (SVD)",
                 3: "config 3: 10M-point clouds, k=%d NormalEstimation + point-to-plane ICP" % args.knn}[cfg]
@@ -434,7 +444,7 @@ def run_pipeline(args, ctx, comm, tgt, src, n, rank, world, fence, gen_s):
         "roofline": {"bound": "hbm", "kernel": "vg_* (VoxelGrid of both clouds, wall time of the two filter() calls)",
                      "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "alg_bytes_per_input_point": B_ALG_VOXEL},
-        "cpu_baseline": None if args.no_cpu_baseline or world > 1 else cpu_pipeline(args, tgt, src),
+        "cpu_baseline": cpu_pipeline(args, tgt, src) if args.full and not args.no_cpu_baseline and world == 1 else None,
         "stages_ms": {k: round(float(np.mean(v)), 3) for k, v in stage_ms.items()},
         "result": {"T_minus_T_gt_frobenius": float(np.linalg.norm(info["T"] - synth.ground_truth_transform()))},
         "setup": {"synth_gen_s": round(gen_s, 1), "commit": git_head()},

@@ -133,7 +133,7 @@ def run_config5(args, ctx, comm, rank, local_rank, world, fence):
     if rank != 0:
         return None
     cpu = None
-    if world == 1 and not getattr(args, "no_cpu_baseline", False):
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_config5(args, n, src, max_dist)
     ncorr = float(sum(s["num_correspondences"] for s in steps))       # all-reduced: the whole job's count
     search_ms = sum(s["search_ms"] for s in steps)

@@ -14,16 +14,16 @@ timeout 1200 python -m pytest tests -m gpu -q > $OUT/tests.log 2>&1; grep -E "pa
 bash scripts/profile_gpu.sh $TAG "trace sq1 sq2 fetch write" > $OUT/prof.log 2>&1
 cp gpurun_out/prof_$TAG/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
 cp gpurun_out/prof_$TAG/summary.txt $OUT/prof_summary.txt 2>/dev/null
-timeout 600 python bench.py > $OUT/bench3.json 2> $OUT/bench3.err
-timeout 300 python bench.py --config 2 > $OUT/bench2.json 2> $OUT/bench2.err
-timeout 300 python bench.py --config 4 > $OUT/bench4.json 2> $OUT/bench4.err
+timeout 600 python bench.py --full > $OUT/bench3.json 2> $OUT/bench3.err
+timeout 300 python bench.py --full --config 2 > $OUT/bench2.json 2> $OUT/bench2.err
+timeout 300 python bench.py --full --config 4 > $OUT/bench4.json 2> $OUT/bench4.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --rejectors median,trimmed > $OUT/bench3_rejectors.json 2> $OUT/bench3_rejectors.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --reciprocal > $OUT/bench3_reciprocal.json 2> $OUT/bench3_reciprocal.err
 for r in 0 1 2 3 4 5 6 7; do
   timeout 300 python bench.py --config 5 --points 100000000 --virtual-world 8 --virtual-rank $r > $OUT/bench5_100M_rank$r.json 2> $OUT/bench5_100M_rank$r.err
 done
 timeout 300 python bench.py --config 5 --points 100000000 --virtual-world 8 --virtual-rank 3 --full-pass > $OUT/bench5_100M_rank3_fullpass.json 2> $OUT/bench5_100M_rank3_fullpass.err
-timeout 600 python bench.py --config 5 --points 100000000 > $OUT/bench5_100M_1gpu.json 2> $OUT/bench5_100M_1gpu.err
+timeout 600 python bench.py --full --config 5 --points 100000000 > $OUT/bench5_100M_1gpu.json 2> $OUT/bench5_100M_1gpu.err
 timeout 300 python scratch/knn_probe.py 10000000 1 8 > $OUT/knn_probe.log 2>&1
 timeout 300 python scratch/radius_probe.py 10000000 > $OUT/radius_probe.log 2>&1
 timeout 300 python scratch/misc_probe.py > $OUT/misc.log 2>&1

@@ -14,8 +14,8 @@ bash scripts/profile_gpu.sh $TAG "trace fetch write" > $OUT/prof.log 2>&1
 cp gpurun_out/prof_$TAG/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
 cp gpurun_out/prof_$TAG/pmc_traffic.json $OUT/pmc_traffic.json 2>/dev/null
 cp gpurun_out/prof_$TAG/summary.txt $OUT/prof_summary.txt 2>/dev/null
-timeout 600 python bench.py > $OUT/bench3.json 2> $OUT/bench3.err
-timeout 300 python bench.py --config 2 --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err
+timeout 600 python bench.py --full > $OUT/bench3.json 2> $OUT/bench3.err
+timeout 300 python bench.py --full --config 2 --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err
 timeout 300 python bench.py --config 4 --no-cpu-baseline > $OUT/bench4.json 2> $OUT/bench4.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --rejectors median,trimmed > $OUT/bench3_rejectors.json 2> $OUT/bench3_rejectors.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --reciprocal > $OUT/bench3_reciprocal.json 2> $OUT/bench3_reciprocal.err

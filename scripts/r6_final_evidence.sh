@@ -15,18 +15,18 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 
 bash scripts/profile_gpu.sh $TAG "trace sq1 sq2 fetch write" > $OUT/prof.log 2>&1
 cp gpurun_out/prof_$TAG/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
 cp gpurun_out/prof_$TAG/summary.txt $OUT/prof_summary.txt 2>/dev/null
-timeout 600 python bench.py > $OUT/bench3.json 2> $OUT/bench3.err
-timeout 300 python bench.py --config 2 > $OUT/bench2.json 2> $OUT/bench2.err
-timeout 300 python bench.py --config 4 > $OUT/bench4.json 2> $OUT/bench4.err
+timeout 600 python bench.py --full > $OUT/bench3.json 2> $OUT/bench3.err
+timeout 300 python bench.py --full --config 2 > $OUT/bench2.json 2> $OUT/bench2.err
+timeout 300 python bench.py --full --config 4 > $OUT/bench4.json 2> $OUT/bench4.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --rejectors median,trimmed > $OUT/bench3_rejectors.json 2> $OUT/bench3_rejectors.err
 timeout 300 python bench.py --no-cpu-baseline --no-host-align --reciprocal > $OUT/bench3_reciprocal.json 2> $OUT/bench3_reciprocal.err
 for c in cube layers clusters; do
-  timeout 300 python bench.py --cloud $c --no-cpu-baseline --no-host-align > $OUT/bench3_cloud_$c.json 2> $OUT/bench3_cloud_$c.err
+  timeout 300 python bench.py --full --cloud $c --no-cpu-baseline --no-host-align > $OUT/bench3_cloud_$c.json 2> $OUT/bench3_cloud_$c.err
 done
 for r in 0 3 6; do
   timeout 300 python bench.py --config 5 --points 100000000 --virtual-world 8 --virtual-rank $r --no-cpu-baseline > $OUT/bench5_100M_rank$r.json 2> $OUT/bench5_100M_rank$r.err
 done
-timeout 900 python bench.py --config 5 --points 100000000 > $OUT/bench5_100M_1gpu.json 2> $OUT/bench5_100M_1gpu.err
+timeout 900 python bench.py --full --config 5 --points 100000000 > $OUT/bench5_100M_1gpu.json 2> $OUT/bench5_100M_1gpu.err
 N=10000000 bash scratch/prof_build.sh ${TAG}_build > $OUT/index_build_dispatches.log 2>&1
 if [ -f pcl_amd/variants/libpclhip_kdbticks.so ]; then
 PCLHIP_LIB=pcl_amd/variants/libpclhip_kdbticks.so timeout 300 python scratch/kdb_ticks.py 2>&1 | grep -v amdgpu.ids > $OUT/kd_block_kernel_ticks.log
