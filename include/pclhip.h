@@ -648,6 +648,81 @@ PCLHIP_API pclhip_status pclhip_gicp_mahalanobis(pclhip_gicp* gicp, double* out)
 PCLHIP_API pclhip_status pclhip_gicp_fitness_score(pclhip_gicp* gicp, const float T[16], double max_range, double* score,
                                                   uint64_t* nr);
 
+/* ---- NormalDistributionsTransform -----------------------------------------------------------------
+ * Replaces pcl::NormalDistributionsTransform<PointXYZ, PointXYZ> with the RADIUS neighbourhood
+ * (registration/include/pcl/registration/ndt.h, impl/ndt.hpp:79-934) on the voxel Gaussians of
+ * pcl::VoxelGridCovariance (filters/include/pcl/filters/impl/voxel_grid_covariance.hpp:47-367).  The voxel Gaussians and the
+ * index over their centroids are built by the first call that needs them and cached until the target, the resolution,
+ * min_points_per_voxel or min_covar_eigvalue_mult changes (ndt.h:121-141, 351-364).
+ * Not built (PCLHIP_ERR_STATE / refused by the bindings): the DIRECT27 / 26 / 7 / 1 neighbourhoods, source subsets
+ * (setIndices), multi-GPU, NormalDistributionsTransform2D. */
+typedef struct pclhip_ndt pclhip_ndt;
+enum { PCLHIP_NDT_RADIUS = 0, PCLHIP_NDT_DIRECT27 = 1, PCLHIP_NDT_DIRECT26 = 2, PCLHIP_NDT_DIRECT7 = 3, PCLHIP_NDT_DIRECT1 = 4 };
+typedef struct {
+  float resolution;                        /* ndt.h:680 resolution_, default 1.0f */
+  int max_iterations;                      /* impl/ndt.hpp:76, default 35 */
+  double step_size;                        /* ndt.h:683 step_size_, default 0.1 */
+  double outlier_ratio;                    /* ndt.h:687 outlier_ratio_, default 0.55 */
+  double transformation_epsilon;           /* impl/ndt.hpp:75, default 0.1; compared with a SQUARED translation (:190-200) */
+  double transformation_rotation_epsilon;  /* registration.h, default 0 */
+  double min_covar_eigvalue_mult;          /* voxel_grid_covariance.h:572, default 0.01 */
+  int min_points_per_voxel;                /* voxel_grid_covariance.h:571, default 6; values below 3 count as 3 (:214-225) */
+  int neighborhood_search_method;          /* PCLHIP_NDT_RADIUS (the reference's default); the others are refused */
+} pclhip_ndt_params;
+typedef struct {
+  float final_transformation[16];   /* row-major; identity when the voxel grid holds no cell (impl/ndt.hpp:86-90) */
+  float last_transformation[16];    /* transformation_: the last outer iteration's step as a matrix */
+  int nr_iterations;                /* outer iterations */
+  int converged;
+  double score;                     /* the score at the final transformation */
+  double transformation_likelihood; /* trans_likelihood_ = score / source size */
+  uint64_t num_cells;               /* voxel Gaussians of the target */
+  uint64_t num_pairs;               /* (point, cell) pairs of the last evaluation */
+  int evaluations_full;             /* passes: score + gradient + Hessian, */
+  int evaluations_gradient;         /* ... score + gradient (line-search trials), */
+  int evaluations_hessian;          /* ... Hessian only (after a line search that iterated) */
+  int trace_count;                  /* entries written to the trace buffer */
+  double cells_ms;                  /* wall time of the voxel Gaussians + their index built by this call (0 when cached) */
+  double eval_ms_full;              /* GPU time of the passes by variant, incl. their reductions (HIP events) */
+  double eval_ms_gradient;
+  double eval_ms_hessian;
+  double total_ms;                  /* wall time of the call */
+} pclhip_ndt_result;
+typedef struct {                    /* one entry per outer iteration (pclhip_ndt_set_trace) */
+  double step_length;               /* what computeStepLengthMT returned */
+  int line_search_trials;           /* iterations of its More-Thuente loop */
+  int reserved;
+  double score;                     /* at the accepted step */
+  float transformation[16];         /* final_transformation_ after this iteration */
+} pclhip_ndt_trace;
+PCLHIP_API void pclhip_ndt_params_default(pclhip_ndt_params* p);
+PCLHIP_API pclhip_status pclhip_ndt_create(pclhip_ctx* ctx, pclhip_ndt** out);
+PCLHIP_API void pclhip_ndt_destroy(pclhip_ndt* ndt);
+/* setInputTarget / setInputSource: strided records (x y z first), host or device; the registration keeps its own copy. */
+PCLHIP_API pclhip_status pclhip_ndt_set_target(pclhip_ndt* ndt, const void* points, size_t stride_bytes, uint64_t n);
+PCLHIP_API pclhip_status pclhip_ndt_set_source(pclhip_ndt* ndt, const void* points, size_t stride_bytes, uint64_t n);
+/* Optional per-outer-iteration record of the next alignments (NULL / 0: none); the buffer must outlive them. */
+PCLHIP_API pclhip_status pclhip_ndt_set_trace(pclhip_ndt* ndt, pclhip_ndt_trace* buf, int capacity);
+/* Registration::align -> computeTransformation (impl/ndt.hpp:79-207).  guess: row-major 4x4 or NULL. */
+PCLHIP_API pclhip_status pclhip_ndt_align(pclhip_ndt* ndt, const pclhip_ndt_params* params, const float guess[16],
+                                         pclhip_ndt_result* result);
+/* One derivative pass at the transformation vector x = (tx ty tz roll pitch yaw) (computeDerivatives, impl/ndt.hpp:209-304;
+ * exposed for tests).  variant 0: score, g[6] and H[36] (row-major); 1: score and gradient (H = 0); 2: computeHessian
+ * (score = 0, g = 0).  pairs (optional): the (point, cell) pairs within the resolution. */
+PCLHIP_API pclhip_status pclhip_ndt_evaluate(pclhip_ndt* ndt, const pclhip_ndt_params* params, const double x[6], int variant,
+                                            double* score, double g[6], double H[36], uint64_t* pairs);
+/* The voxel Gaussians in ascending voxel id (exposed for tests): *count always; each non-NULL host array receives one row
+ * per cell when capacity >= *count (PCLHIP_ERR_OVERFLOW otherwise): centroids 3 floats, means 3 doubles, cov (the raw
+ * covariance of voxel_grid_covariance.hpp:326) and icov 9 doubles row-major, point counts, voxel ids, validity (0: the
+ * cell failed the eigenvalue test; it stays in the centroid cloud with a zero icov, as in the reference). */
+PCLHIP_API pclhip_status pclhip_ndt_cells(pclhip_ndt* ndt, const pclhip_ndt_params* params, uint64_t* count, float* centroids,
+                                         double* means, double* cov, double* icov, int32_t* npoints, int32_t* voxel_ids,
+                                         uint8_t* valid, uint64_t capacity);
+/* Registration::getFitnessScore (impl/registration.hpp:132-168) through pclhip_icp_fitness_score (an index over the
+ * target's points is built on first use); T NULL: the final transformation of the last alignment. */
+PCLHIP_API pclhip_status pclhip_ndt_fitness_score(pclhip_ndt* ndt, const float T[16], double max_range, double* score,
+                                                 uint64_t* nr);
+
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/
  * voxel_grid.hpp:597-814) with downsample_all_data and the optional pass-through filter in front of

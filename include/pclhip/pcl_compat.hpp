@@ -1314,6 +1314,103 @@ class GeneralizedIterativeClosestPoint : public IterativeClosestPoint<PointSourc
   bool src_cov_dirty_ = false, tgt_cov_dirty_ = false;
 };
 
+// pcl::NormalDistributionsTransform<PointSource, PointTarget> (registration/include/pcl/registration/ndt.h, impl/ndt.hpp)
+// on the C ABI's pclhip_ndt: the voxel Gaussians of the target are built by the first align() and cached until the target,
+// the resolution or the minimum points per voxel changes.  Only NeighborSearchMethod::RADIUS (the reference's default) is
+// built; the DIRECT neighbourhoods and source subsets (setIndices) are refused with std::logic_error.
+enum class NeighborSearchMethod { RADIUS, DIRECT27, DIRECT26, DIRECT7, DIRECT1 };  // ndt.h:59-65
+
+template <typename PointSource, typename PointTarget>
+class NormalDistributionsTransform : public Registration<PointSource, PointTarget> {
+  using Base = Registration<PointSource, PointTarget>;
+ public:
+  using PointCloudSource = typename Base::PointCloudSource;
+  using Matrix4 = typename Base::Matrix4;
+  using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
+  using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
+  using Ptr = std::shared_ptr<NormalDistributionsTransform<PointSource, PointTarget>>;
+  NormalDistributionsTransform() : NormalDistributionsTransform(Context::defaultContext()) {}
+  explicit NormalDistributionsTransform(Context::Ptr ctx) : Base(std::move(ctx)) {  // impl/ndt.hpp:68-77
+    this->reg_name_ = "NormalDistributionsTransform";
+    pclhip_ndt_params_default(&p_);
+    this->transformation_epsilon_ = p_.transformation_epsilon;
+    this->max_iterations_ = p_.max_iterations;
+  }
+  ~NormalDistributionsTransform() override { if (ndt_) pclhip_ndt_destroy(ndt_); }
+
+  void setInputSource(const PointCloudSourceConstPtr& cloud) override { Base::setInputSource(cloud); source_dirty_ = true; }
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) override { Base::setInputTarget(cloud); target_dirty_ = true; }  // ndt.h:121-127
+  void setIndices(const IndicesPtr& indices) override { refuseIndices(indices != nullptr); }
+  void setIndices(const IndicesConstPtr& indices) override { refuseIndices(indices != nullptr); }
+  void setResolution(float resolution) { p_.resolution = resolution; }  // ndt.h:133-141: the grid is rebuilt by the next align
+  float getResolution() const { return p_.resolution; }
+  void setMinPointPerVoxel(unsigned int n) { p_.min_points_per_voxel = int(n); }  // ndt.h:130
+  void setStepSize(double step_size) { p_.step_size = step_size; }
+  double getStepSize() const { return p_.step_size; }
+  void setOutlierRatio(double r) { p_.outlier_ratio = r; }
+  double getOutlierRatio() const { return p_.outlier_ratio; }
+  void setNeighborhoodSearchMethod(NeighborSearchMethod method) {  // ndt.h:243-254
+    if (method != NeighborSearchMethod::RADIUS)
+      throw std::logic_error("NormalDistributionsTransform: the DIRECT27 / DIRECT26 / DIRECT7 / DIRECT1 neighbourhoods are "
+                             "not supported (RADIUS only)");
+  }
+  NeighborSearchMethod getNeighborhoodSearchMethod() const { return NeighborSearchMethod::RADIUS; }
+  void setNumberOfThreads(unsigned int) {}  // the OpenMP thread count of the reference's derivative loop: no effect
+  double getTransformationLikelihood() const { return result_.transformation_likelihood; }
+  double getTransformationProbability() const { return result_.transformation_likelihood; }
+  int getFinalNumIteration() const { return this->nr_iterations_; }
+  const pclhip_ndt_result& lastResult() const { return result_; }
+
+  // Registration::getFitnessScore (impl/registration.hpp:132-168)
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
+    double score = std::numeric_limits<double>::max();
+    if (!this->initCompute() || !ensureNdt()) return score;
+    pclhip_ndt_fitness_score(ndt_, this->final_transformation_.m, max_range, &score, nullptr);
+    return score;
+  }
+
+ protected:
+  void refuseIndices(bool given) {
+    if (given) throw std::logic_error("NormalDistributionsTransform: source subsets (setIndices) are not supported");
+  }
+  bool ensureNdt() {
+    if (!ndt_ && pclhip_ndt_create(this->ctx_->get(), &ndt_) != PCLHIP_OK) return false;
+    if (target_dirty_) {
+      if (!this->target_ ||
+          pclhip_ndt_set_target(ndt_, this->target_->points.data(), sizeof(PointTarget), this->target_->size()) != PCLHIP_OK)
+        return false;
+      target_dirty_ = false;
+    }
+    if (source_dirty_) {
+      if (pclhip_ndt_set_source(ndt_, this->input_->points.data(), sizeof(PointSource), this->input_->size()) != PCLHIP_OK)
+        return false;
+      source_dirty_ = false;
+    }
+    return true;
+  }
+  void computeTransformation(PointCloudSource& output, const Matrix4& guess) override {  // impl/ndt.hpp:79-207
+    this->converged_ = false;
+    this->nr_iterations_ = 0;
+    if (!ensureNdt()) return;
+    p_.max_iterations = this->max_iterations_;
+    p_.transformation_epsilon = this->transformation_epsilon_;
+    p_.transformation_rotation_epsilon = this->transformation_rotation_epsilon_;
+    if (pclhip_ndt_align(ndt_, &p_, guess.m, &result_) != PCLHIP_OK) return;
+    std::memcpy(this->final_transformation_.m, result_.final_transformation, sizeof result_.final_transformation);
+    std::memcpy(this->transformation_.m, result_.last_transformation, sizeof result_.last_transformation);
+    this->converged_ = result_.converged != 0;
+    this->nr_iterations_ = result_.nr_iterations;
+    output = *this->input_;  // the trial clouds are transformPointCloud(*input_, output, final_transformation_) (:841)
+    pclhip_transform_cloud(this->ctx_->get(), this->final_transformation_.m, 1, output.points.data(), output.points.data(),
+                           sizeof(PointSource), output.size(), 0);
+  }
+
+  pclhip_ndt_params p_;
+  pclhip_ndt_result result_ = {};
+  pclhip_ndt* ndt_ = nullptr;
+  bool target_dirty_ = true, source_dirty_ = true;
+};
+
 // pcl::io::loadPCDFile / savePCDFile{ASCII,Binary,BinaryCompressed} (io/include/pcl/io/pcd_io.h:685-800)
 // for the point types of this header: records of sizeof(PointT) bytes, normals at +16 when the type has them.
 namespace io {

@@ -8,6 +8,7 @@ from .api import (Communicator, Context, CorrespondenceEstimation, Correspondenc
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, GeneralizedIterativeClosestPoint,
                   IterativeClosestPoint,
-                  IterativeClosestPointWithNormals, KdTree, NormalEstimation, RadiusOutlierRemoval,
+                  IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
+                  RadiusOutlierRemoval,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

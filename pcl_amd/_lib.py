@@ -74,6 +74,30 @@ class GicpTrace(C.Structure):
                 ("f", C.c_double), ("transformation", C.c_float * 16)]
 
 
+class NdtParams(C.Structure):
+    _fields_ = [("resolution", C.c_float), ("max_iterations", C.c_int), ("step_size", C.c_double),
+                ("outlier_ratio", C.c_double), ("transformation_epsilon", C.c_double),
+                ("transformation_rotation_epsilon", C.c_double), ("min_covar_eigvalue_mult", C.c_double),
+                ("min_points_per_voxel", C.c_int), ("neighborhood_search_method", C.c_int)]
+
+
+class NdtResult(C.Structure):
+    _fields_ = [("final_transformation", C.c_float * 16), ("last_transformation", C.c_float * 16),
+                ("nr_iterations", C.c_int), ("converged", C.c_int), ("score", C.c_double),
+                ("transformation_likelihood", C.c_double), ("num_cells", C.c_uint64), ("num_pairs", C.c_uint64),
+                ("evaluations_full", C.c_int), ("evaluations_gradient", C.c_int), ("evaluations_hessian", C.c_int),
+                ("trace_count", C.c_int), ("cells_ms", C.c_double), ("eval_ms_full", C.c_double),
+                ("eval_ms_gradient", C.c_double), ("eval_ms_hessian", C.c_double), ("total_ms", C.c_double)]
+
+
+class NdtTrace(C.Structure):
+    _fields_ = [("step_length", C.c_double), ("line_search_trials", C.c_int), ("reserved", C.c_int),
+                ("score", C.c_double), ("transformation", C.c_float * 16)]
+
+
+NDT_RADIUS, NDT_DIRECT27, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = 0, 1, 2, 3, 4
+
+
 class ConvergenceState(C.Structure):
     _fields_ = [("prev_mse", C.c_double), ("iterations_similar_transforms", C.c_int), ("convergence_state", C.c_int)]
 
@@ -154,6 +178,18 @@ SIGNATURES = {
     "pclhip_gicp_mahalanobis": (C.c_int, [_vp, _vp]),
     "pclhip_gicp_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
                                             C.POINTER(_u64)]),
+    "pclhip_ndt_params_default": (None, [C.POINTER(NdtParams)]),
+    "pclhip_ndt_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "pclhip_ndt_destroy": (None, [_vp]),
+    "pclhip_ndt_set_target": (C.c_int, [_vp, _vp, _sz, _u64]),
+    "pclhip_ndt_set_source": (C.c_int, [_vp, _vp, _sz, _u64]),
+    "pclhip_ndt_set_trace": (C.c_int, [_vp, C.POINTER(NdtTrace), C.c_int]),
+    "pclhip_ndt_align": (C.c_int, [_vp, C.POINTER(NdtParams), C.POINTER(C.c_float), C.POINTER(NdtResult)]),
+    "pclhip_ndt_evaluate": (C.c_int, [_vp, C.POINTER(NdtParams), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_u64)]),
+    "pclhip_ndt_cells": (C.c_int, [_vp, C.POINTER(NdtParams), C.POINTER(_u64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
+    "pclhip_ndt_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
+                                           C.POINTER(_u64)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

@@ -1364,6 +1364,229 @@ class GeneralizedIterativeClosestPoint:
             pass
 
 
+class NormalDistributionsTransform:
+    """pcl::NormalDistributionsTransform<PointXYZ, PointXYZ> (registration/include/pcl/registration/ndt.h, impl/ndt.hpp)
+    with the RADIUS neighbourhood.  The voxel Gaussians of the target (VoxelGridCovariance) are built by the first call
+    that needs them and cached until the target, the resolution or min_points_per_voxel changes."""
+
+    RADIUS, DIRECT27, DIRECT26, DIRECT7, DIRECT1 = (_lib.NDT_RADIUS, _lib.NDT_DIRECT27, _lib.NDT_DIRECT26, _lib.NDT_DIRECT7,
+                                                    _lib.NDT_DIRECT1)
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.p = _lib.NdtParams()
+        self.lib.pclhip_ndt_params_default(C.byref(self.p))
+        self.h = None
+        self.src = None
+        self.target = None
+        self._tgt_dirty = True
+        self._src_dirty = True
+        self.result = None
+        self.trace = []
+        self.ctx._adopt(self)
+
+    def _release(self):
+        self._drop()
+
+    def _drop(self):
+        if getattr(self, "h", None):
+            if self.ctx.h is not None:
+                self.lib.pclhip_ndt_destroy(self.h)
+            self.h = None
+        self._tgt_dirty = self._src_dirty = True
+
+    def getClassName(self):
+        return "NormalDistributionsTransform"
+
+    # --- inputs (ndt.h:121-141, registration.h:195-240) ---
+    def setInputTarget(self, cloud):
+        """ndt.h:121-127: a new target rebuilds the voxel grid."""
+        self.target = cloud
+        self._tgt_dirty = True
+
+    def setInputSource(self, cloud):
+        self.src = cloud
+        self._src_dirty = True
+
+    def setSearchMethodTarget(self, tree, force_no_recompute=False):
+        """Accepted: NormalDistributionsTransform searches its voxel grid, not the target's tree."""
+
+    def setSearchMethodSource(self, tree, force_no_recompute=False):
+        """Accepted: see setSearchMethodTarget."""
+
+    def setNumberOfThreads(self, n):
+        """Accepted, no effect (impl/ndt.hpp:49-66: the OpenMP thread count of the derivative loop)."""
+
+    def setIndices(self, indices):
+        if indices is not None:
+            raise NotImplementedError("NormalDistributionsTransform: source subsets (setIndices) are not supported")
+
+    def setCommunicator(self, comm):
+        raise NotImplementedError("NormalDistributionsTransform: multi-GPU registration is not supported")
+
+    # --- parameters (ndt.h:130-260) ---
+    def setResolution(self, r):
+        """ndt.h:133-141: a new resolution rebuilds the voxel grid (on the next call that needs it)."""
+        self.p.resolution = float(r)
+
+    def getResolution(self):
+        return float(self.p.resolution)
+
+    def setStepSize(self, s):
+        self.p.step_size = float(s)
+
+    def getStepSize(self):
+        return float(self.p.step_size)
+
+    def setOutlierRatio(self, r):
+        self.p.outlier_ratio = float(r)
+
+    def getOutlierRatio(self):
+        return float(self.p.outlier_ratio)
+
+    def setMinPointPerVoxel(self, n):
+        self.p.min_points_per_voxel = int(n)
+
+    def setMaximumIterations(self, n):
+        self.p.max_iterations = int(n)
+
+    def getMaximumIterations(self):
+        return int(self.p.max_iterations)
+
+    def setTransformationEpsilon(self, e):
+        self.p.transformation_epsilon = float(e)
+
+    def getTransformationEpsilon(self):
+        return float(self.p.transformation_epsilon)
+
+    def setTransformationRotationEpsilon(self, e):
+        self.p.transformation_rotation_epsilon = float(e)
+
+    def setNeighborhoodSearchMethod(self, method):
+        """ndt.h:243-254.  Only NeighborSearchMethod::RADIUS (the reference's default) is built."""
+        if int(method) != _lib.NDT_RADIUS:
+            raise NotImplementedError("NormalDistributionsTransform: the DIRECT27 / DIRECT26 / DIRECT7 / DIRECT1 "
+                                      "neighbourhoods are not supported (RADIUS only)")
+        self.p.neighborhood_search_method = int(method)
+
+    def _ensure(self):
+        if self.target is None:
+            raise ValueError("No input target dataset was given!")
+        if self.src is None:
+            raise ValueError("No input source dataset was given!")
+        if self.h is None:
+            h = C.c_void_p()
+            check(self.lib.pclhip_ndt_create(self.ctx.h, C.byref(h)), self.ctx.h)
+            self.h = h
+        if self._tgt_dirty:
+            ptr, stride, n, keep = _cloud(self.target)
+            check(self.lib.pclhip_ndt_set_target(self.h, ptr, stride, n), self.ctx.h)
+            self._tgt_dirty = False
+        if self._src_dirty:
+            ptr, stride, n, keep = _cloud(self.src)
+            check(self.lib.pclhip_ndt_set_source(self.h, ptr, stride, n), self.ctx.h)
+            self._src_dirty = False
+
+    def align(self, guess=None, trace_capacity=256, want_output=False):
+        """Registration::align -> computeTransformation (impl/ndt.hpp:79-207).  Returns the registered source (the input
+        moved by the final transformation, transformPointCloud's order) when want_output, else None; results via
+        getFinalTransformation() / hasConverged(); per outer iteration the step length, the line search's trials, the
+        score and the transformation in self.trace."""
+        self._ensure()
+        buf = (_lib.NdtTrace * max(1, int(trace_capacity)))()
+        check(self.lib.pclhip_ndt_set_trace(self.h, buf, int(trace_capacity)), self.ctx.h)
+        r = _lib.NdtResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16)
+        try:
+            check(self.lib.pclhip_ndt_align(self.h, C.byref(self.p), _fp(g) if g is not None else None, C.byref(r)),
+                  self.ctx.h)
+        finally:
+            self.lib.pclhip_ndt_set_trace(self.h, None, 0)
+        self.result = r
+        self.trace = [dict(step_length=float(t.step_length), line_search_trials=int(t.line_search_trials),
+                           score=float(t.score), transformation=np.array(t.transformation, np.float32).reshape(4, 4))
+                      for t in buf[:r.trace_count]]
+        if not want_output:
+            return None
+        ptr, stride, n, keep = _cloud(self.src)
+        out = keep.clone() if _is_torch(self.src) else keep.copy()
+        optr = C.c_void_p(out.data_ptr() if _is_torch(self.src) else out.ctypes.data)
+        check(self.lib.pclhip_transform_cloud(self.ctx.h, _fp(np.ascontiguousarray(self.getFinalTransformation()).reshape(16)),
+                                              1, ptr, optr, stride, n, 0), self.ctx.h)
+        return out
+
+    def getFinalTransformation(self):
+        return np.array(self.result.final_transformation, np.float32).reshape(4, 4)
+
+    def getLastIncrementalTransformation(self):
+        return np.array(self.result.last_transformation, np.float32).reshape(4, 4)
+
+    def hasConverged(self):
+        return bool(self.result.converged)
+
+    def getFinalNumIteration(self):
+        return int(self.result.nr_iterations)
+
+    @property
+    def nr_iterations_(self):
+        return int(self.result.nr_iterations)
+
+    def getTransformationLikelihood(self):
+        return float(self.result.transformation_likelihood)
+
+    def getTransformationProbability(self):
+        return self.getTransformationLikelihood()
+
+    def getFitnessScore(self, max_range=float(np.finfo(np.float64).max)):
+        """Registration::getFitnessScore (impl/registration.hpp:132-168) with the final transformation."""
+        self._ensure()
+        T = np.ascontiguousarray(self.getFinalTransformation(), np.float32).reshape(16)
+        score = C.c_double(0.0)
+        nr = C.c_uint64(0)
+        check(self.lib.pclhip_ndt_fitness_score(self.h, _fp(T), C.c_double(max_range), C.byref(score), C.byref(nr)),
+              self.ctx.h)
+        return float(score.value)
+
+    def evaluate(self, x, variant=0):
+        """One derivative pass at x = (tx ty tz roll pitch yaw): (score, g[6], H[6x6], pairs).  variant 0: all three
+        (computeDerivatives), 1: score and gradient (the line search's trials), 2: Hessian only (computeHessian)."""
+        self._ensure()
+        xv = np.ascontiguousarray(x, np.float64).reshape(6)
+        f = C.c_double(0.0)
+        pairs = C.c_uint64(0)
+        g = np.zeros(6, np.float64)
+        H = np.zeros(36, np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self.lib.pclhip_ndt_evaluate(self.h, C.byref(self.p), xv.ctypes.data_as(dp), int(variant), C.byref(f),
+                                           g.ctypes.data_as(dp), H.ctypes.data_as(dp), C.byref(pairs)), self.ctx.h)
+        return float(f.value), g, H.reshape(6, 6), int(pairs.value)
+
+    def cells(self):
+        """The voxel Gaussians of the target in ascending voxel id: dict(centroids (n, 3) float32, means (n, 3), cov and
+        icov (n, 3, 3) float64, npoints, voxel_ids (n,) int32, valid (n,) bool)."""
+        self._ensure()
+        count = C.c_uint64(0)
+        none = C.c_void_p(None)
+        check(self.lib.pclhip_ndt_cells(self.h, C.byref(self.p), C.byref(count), none, none, none, none, none, none, none, 0),
+              self.ctx.h)
+        n = int(count.value)
+        out = dict(centroids=np.zeros((n, 3), np.float32), means=np.zeros((n, 3), np.float64), cov=np.zeros((n, 3, 3), np.float64),
+                   icov=np.zeros((n, 3, 3), np.float64), npoints=np.zeros(n, np.int32), voxel_ids=np.zeros(n, np.int32),
+                   valid=np.zeros(n, np.uint8))
+        if n:
+            ptr = [C.c_void_p(out[k].ctypes.data) for k in ("centroids", "means", "cov", "icov", "npoints", "voxel_ids", "valid")]
+            check(self.lib.pclhip_ndt_cells(self.h, C.byref(self.p), C.byref(count), *ptr, n), self.ctx.h)
+        out["valid"] = out["valid"].astype(bool)
+        return out
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+
 class VoxelGrid:
     """pcl::VoxelGrid<PointT> for pcl::PointXYZ ((n, 4) clouds) and pcl::PointNormal ((n, 12) clouds): leaf size,
     minimum points per voxel, downsample_all_data, the pass-through filter on one field, the leaf layout."""

@@ -523,6 +523,21 @@ struct OutlierParams {
 pclhip_status outlier_filter(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, const OutlierParams& prm,
                              int32_t* kept, uint64_t* n_kept, int32_t* removed, uint64_t* n_removed, float* mean_dist,
                              double* stats6);
+// NormalDistributionsTransform: the voxel Gaussians of a target cloud (ndt_cells.hpp, compiled into voxelgrid.hip), in
+// ascending voxel id.  Device arrays owned by the struct (ndt_free_cells).
+struct NdtCells {
+  uint32_t count = 0;
+  float4* centroid = nullptr;   // [count] xyz of the float centroid, w = the cell's position (bits): an index built over
+                                // them hands it back in its leaf slots
+  double* rec = nullptr;        // [count * 9] mean[3], inverse covariance c00 c01 c02 c11 c12 c22 (ndt_forms.hpp)
+  double* cov = nullptr;        // [count * 9] the covariance of voxel_grid_covariance.hpp:326 (before the inflation)
+  int32_t* npoints = nullptr;   // [count]
+  int32_t* voxel = nullptr;     // [count] voxel id
+  uint8_t* valid = nullptr;     // [count] 0: the cell failed the eigenvalue test (nr_points = -1 in the reference)
+};
+pclhip_status ndt_build_cells(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, float resolution,
+                              uint32_t min_points_per_voxel, double min_covar_eigvalue_mult, NdtCells* cells);
+void ndt_free_cells(pclhip_ctx* ctx, NdtCells* cells);
 pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d2, bool use_max,
                                  int mode, hipEvent_t* step_events = nullptr);
 // target sharding, after a run of the device-driven loop: the working copies of the groups the last launches did not
@@ -552,5 +567,6 @@ void solve_point_to_plane(const double* sums, float* T);
 void solve_point_to_point(const double* sums, float* T);
 void solve_symmetric(const double* sums, float* T);
 void mat4_mul_f32(const float* A, const float* B, float* C);
+void ndt_newton_direction(const double* H, const double* b, double* delta);
 
 }  // namespace pclhip

@@ -427,3 +427,6 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 
 // StatisticalOutlierRemoval / RadiusOutlierRemoval: their kernels traverse the same index (entry points in api.hip)
 #include "outlier.hpp"
+
+// NormalDistributionsTransform: its derivative pass is a radius traversal of the index over the voxel centroids
+#include "ndt.hpp"

@@ -612,11 +612,39 @@ extern "C" pclhip_status pclhip_voxelgrid_ex(pclhip_ctx* ctx, const void* points
                               normals_offset, out, out_stride, out_n, nullptr, 0, nullptr);
 }
 
+// NormalDistributionsTransform's voxel Gaussians take the grid, the keys, the stable sort and the runs of this filter
+// and replace its centroid stage (ndt_cells_from_runs)
+#include "ndt_cells.hpp"
+
+// `cells` != nullptr: VoxelGridCovariance (the voxel Gaussians of the kept runs instead of the centroid records)
+static pclhip_status voxelgrid_run(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, const float leaf[3],
+                                   uint32_t min_points_per_voxel, int has_z_limits, double z_min, double z_max,
+                                   int downsample_all_data, size_t normals_offset, void* out, size_t out_stride,
+                                   uint64_t* out_n, int32_t* leaf_layout, uint64_t leaf_layout_capacity,
+                                   pclhip_voxelgrid_dims* dims, NdtCells* cells, double min_covar_eigvalue_mult);
+
 extern "C" pclhip_status pclhip_voxelgrid_ex2(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n,
                                               const float leaf[3], uint32_t min_points_per_voxel, int has_z_limits,
                                               double z_min, double z_max, int downsample_all_data, size_t normals_offset,
                                               void* out, size_t out_stride, uint64_t* out_n, int32_t* leaf_layout,
                                               uint64_t leaf_layout_capacity, pclhip_voxelgrid_dims* dims) {
+  return voxelgrid_run(ctx, points, stride, n, leaf, min_points_per_voxel, has_z_limits, z_min, z_max, downsample_all_data,
+                       normals_offset, out, out_stride, out_n, leaf_layout, leaf_layout_capacity, dims, nullptr, 0.0);
+}
+
+pclhip_status pclhip::ndt_build_cells(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, float resolution,
+                                      uint32_t min_points_per_voxel, double min_covar_eigvalue_mult, NdtCells* cells) {
+  const float leaf[3] = {resolution, resolution, resolution};
+  uint64_t count = 0;
+  return voxelgrid_run(ctx, points, stride, n, leaf, min_points_per_voxel, 0, 0.0, 0.0, 0, 0, nullptr, 16, &count, nullptr, 0,
+                       nullptr, cells, min_covar_eigvalue_mult);
+}
+
+static pclhip_status voxelgrid_run(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, const float leaf[3],
+                                   uint32_t min_points_per_voxel, int has_z_limits, double z_min, double z_max,
+                                   int downsample_all_data, size_t normals_offset, void* out, size_t out_stride,
+                                   uint64_t* out_n, int32_t* leaf_layout, uint64_t leaf_layout_capacity,
+                                   pclhip_voxelgrid_dims* dims, NdtCells* cells, double min_covar_eigvalue_mult) {
   if (!ctx || !leaf || !out_n) return PCLHIP_ERR_INVALID;
   *out_n = 0;
   if (dims) std::memset(dims, 0, sizeof *dims);
@@ -632,7 +660,7 @@ extern "C" pclhip_status pclhip_voxelgrid_ex2(pclhip_ctx* ctx, const void* point
                                            size_t(((has_z_limits >> 8) & 0xFF) ? ((has_z_limits >> 8) & 0xFF) : 3) * 4 <= stride),
                  "filter limits: bit 0 on, bit 1 negative, bits 8..15 = 1 + float position of the field inside the record");
   if (n == 0) return PCLHIP_OK;
-  PCLHIP_REQUIRE(ctx, points && (out || dims_only), "null buffer");
+  PCLHIP_REQUIRE(ctx, points && (out || dims_only || cells), "null buffer");
   PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   dev_reserve_for_points(ctx, n);
   hipStream_t s = ctx->stream;
@@ -814,6 +842,11 @@ extern "C" pclhip_status pclhip_voxelgrid_ex2(pclhip_ctx* ctx, const void* point
   }
 
   if (d_layout) hipLaunchKernelGGL(vg_layout_kernel, dim3((nruns + 255) / 256), dim3(256), 0, s, keys_sorted, run_start, keep, keep_scan, nruns, d_layout);
+
+  if (cells) {
+    return ndt_cells_from_runs(ctx, dp, stride, vals_sorted, keys_sorted, run_start, keep, keep_scan, nruns, total,
+                               min_covar_eigvalue_mult, cells);
+  }
 
   // --- centroids ---
   void* d_out = out;

@@ -1,0 +1,488 @@
+"""A CPU restatement of NormalDistributionsTransform with the RADIUS neighbourhood (registration/include/pcl/registration/
+ndt.h, impl/ndt.hpp:79-934) on the voxel Gaussians of VoxelGridCovariance (filters/include/pcl/filters/impl/
+voxel_grid_covariance.hpp:47-367) for the NDT tests: numpy, fp64.
+
+Written per pair from the reference's loops: sequential sums inside a voxel (np.cumsum; numpy's sum is pairwise),
+np.linalg.eigh / inv / svd for the dense steps, the radius neighbours of a point taken from the 27 voxels around it with
+the float32 test (dx^2 + dy^2) + dz^2 < float32(r * r), the full 6 x 6 pair Hessian as the reference writes it.  The float
+arithmetic of convertTransform, of the Euler extraction and of the transforms follows the library's operation order
+(pcl_amd/csrc/ndt_forms.hpp, icp_xform.hpp): per-operation float32 rounding, sin / cos / atan2 in double rounded to float
+(the reference takes them in float: a difference at the ulp level of a float angle, documented in ndt_forms.hpp)."""
+import math
+
+import numpy as np
+
+F = np.float32
+
+
+# ---- voxel Gaussians ------------------------------------------------------------------------------------------------
+def voxel_cells(tgt, resolution, min_points=6, mult=0.01):
+    """VoxelGridCovariance::applyFilter: dict(centroids, means, cov (raw, :326), icov, npoints, voxel_ids, valid) in
+    ascending voxel id; cells that fail the eigenvalue test stay, with a zero icov."""
+    min_points = max(3, int(min_points))
+    p = np.ascontiguousarray(tgt[:, :3], F)
+    keep = np.isfinite(p).all(1)
+    p = p[keep]
+    empty = dict(centroids=np.zeros((0, 3), F), means=np.zeros((0, 3)), cov=np.zeros((0, 3, 3)), icov=np.zeros((0, 3, 3)),
+                 npoints=np.zeros(0, np.int32), voxel_ids=np.zeros(0, np.int32), valid=np.zeros(0, bool))
+    if len(p) == 0:
+        return empty
+    inv = F(1.0) / F(resolution)
+    mn, mx = p.min(0), p.max(0)
+    min_b = np.floor(mn * inv).astype(np.int64)
+    max_b = np.floor(mx * inv).astype(np.int64)
+    div = max_b - min_b + 1
+    mul = np.array([1, div[0], div[0] * div[1]])
+    idx = (np.floor(p * inv).astype(np.int64) - min_b) @ mul
+    order = np.argsort(idx, kind="stable")
+    sidx = idx[order]
+    starts = np.flatnonzero(np.r_[True, sidx[1:] != sidx[:-1]])
+    ends = np.r_[starts[1:], len(sidx)]
+    out = {k: [] for k in empty}
+    for s, e in zip(starts, ends):
+        n = int(e - s)
+        if n < min_points:
+            continue
+        q = p[order[s:e]]
+        c = np.cumsum(q, axis=0, dtype=F)[-1] / F(n)
+        qd = q.astype(np.float64)
+        pt_sum = np.cumsum(qd, axis=0)[-1]
+        cov_sum = np.cumsum(qd[:, :, None] * qd[:, None, :], axis=0)[-1]
+        mean = pt_sum / n
+        cov = (cov_sum - np.outer(pt_sum, mean)) / (n - 1.0)
+        w, V = np.linalg.eigh(cov)
+        ok = True
+        icov = np.zeros((3, 3))
+        if w[0] < -1e-12 or w[1] < -1e-12 or w[2] <= 0:
+            ok = False
+        else:
+            C = cov
+            floor_ = mult * w[2]
+            if w[0] < floor_:
+                w = w.copy()
+                w[0] = floor_
+                if w[1] < floor_:
+                    w[1] = floor_
+                C = V @ np.diag(w) @ np.linalg.inv(V)
+            icov = np.linalg.inv(C)
+            if icov.max() == np.inf or icov.min() == -np.inf:
+                ok = False
+        out["centroids"].append(c)
+        out["means"].append(mean)
+        out["cov"].append(cov)
+        out["icov"].append(icov)
+        out["npoints"].append(n)
+        out["voxel_ids"].append(int(sidx[s]))
+        out["valid"].append(ok)
+    if not out["npoints"]:
+        return empty
+    return dict(centroids=np.array(out["centroids"], F), means=np.array(out["means"]), cov=np.array(out["cov"]),
+                icov=np.array(out["icov"]), npoints=np.array(out["npoints"], np.int32),
+                voxel_ids=np.array(out["voxel_ids"], np.int32), valid=np.array(out["valid"], bool))
+
+
+# ---- float forms ------------------------------------------------------------------------------------------------------
+def _angle_axis(angle, ax):
+    a = F(angle)
+    s, c = F(math.sin(float(a))), F(math.cos(float(a)))
+    d = (F(1) - c) * F(1) * F(1) + c
+    u, v = (ax + 1) % 3, (ax + 2) % 3
+    R = np.zeros((3, 3), F)
+    R[ax, ax], R[u, u], R[v, v] = d, c, c
+    R[u, v], R[v, u] = -s, s
+    return R
+
+
+def _mul3f(A, B):
+    C = np.zeros((3, 3), F)
+    for r in range(3):
+        for c in range(3):
+            C[r, c] = (A[r, 0] * B[0, c] + A[r, 1] * B[1, c]) + A[r, 2] * B[2, c]
+    return C
+
+
+def convert_transform(x):
+    """ndt.h:293-313: Translation * AngleAxis(x) * AngleAxis(y) * AngleAxis(z) in float."""
+    R = _mul3f(_mul3f(_angle_axis(x[3], 0), _angle_axis(x[4], 1)), _angle_axis(x[5], 2))
+    T = np.eye(4, dtype=F)
+    T[:3, :3] = R
+    T[:3, 3] = (F(x[0]), F(x[1]), F(x[2]))
+    return T
+
+
+def euler_from(T):
+    """translation and rotation().eulerAngles(0, 1, 2) of a float transform (impl/ndt.hpp:113-125)."""
+    T = np.asarray(T, F)
+    m = lambda r, c: float(T[r, c])  # noqa: E731
+    r0 = math.atan2(m(1, 2), m(2, 2))
+    c2 = float(F(math.sqrt(float(T[0, 0] * T[0, 0] + T[0, 1] * T[0, 1]))))
+    if r0 > 0.0:
+        r0 -= math.pi
+        r1 = math.atan2(-m(0, 2), -c2)
+    else:
+        r1 = math.atan2(-m(0, 2), c2)
+    r0 = float(F(r0))
+    s1, c1 = float(F(math.sin(r0))), float(F(math.cos(r0)))
+    r2 = math.atan2(s1 * m(2, 0) - c1 * m(1, 0), c1 * m(1, 1) - s1 * m(2, 1))
+    return np.array([m(0, 3), m(1, 3), m(2, 3), float(F(-r0)), float(F(-r1)), float(F(-r2))])
+
+
+def transform_se3(T, p):
+    """Transformer<float>::se3 (transforms.hpp:117-123): r0 x + (r1 y + (r2 z + r3))."""
+    T = np.asarray(T, F)
+    p = np.asarray(p, F)
+    return np.stack([T[r, 0] * p[:, 0] + (T[r, 1] * p[:, 1] + (T[r, 2] * p[:, 2] + T[r, 3])) for r in range(3)], 1)
+
+
+def gauss_constants(resolution, outlier_ratio):
+    c1 = 10 * (1 - outlier_ratio)
+    c2 = outlier_ratio / math.pow(float(F(resolution)), 3)
+    d3 = -math.log(c2)
+    d1 = -math.log(c1 + c2) - d3
+    d2 = -2 * math.log((-math.log(c1 * math.exp(-0.5) + c2) - d3) / d1)
+    return d1, d2
+
+
+def angle_tables(x):
+    """computeAngleDerivatives (impl/ndt.hpp:306-389)."""
+    cx, sx = (1.0, 0.0) if abs(x[3]) < 10e-5 else (math.cos(x[3]), math.sin(x[3]))
+    cy, sy = (1.0, 0.0) if abs(x[4]) < 10e-5 else (math.cos(x[4]), math.sin(x[4]))
+    cz, sz = (1.0, 0.0) if abs(x[5]) < 10e-5 else (math.cos(x[5]), math.sin(x[5]))
+    aj = np.array([[-sx * sz + cx * sy * cz, -sx * cz - cx * sy * sz, -cx * cy],
+                   [cx * sz + sx * sy * cz, cx * cz - sx * sy * sz, -sx * cy],
+                   [-sy * cz, sy * sz, cy],
+                   [sx * cy * cz, -sx * cy * sz, sx * sy],
+                   [-cx * cy * cz, cx * cy * sz, -cx * sy],
+                   [-cy * sz, -cy * cz, 0],
+                   [cx * cz - sx * sy * sz, -cx * sz - sx * sy * cz, 0],
+                   [sx * cz + cx * sy * sz, cx * sy * cz - sx * sz, 0]])
+    ah = np.array([[-cx * sz - sx * sy * cz, -cx * cz + sx * sy * sz, sx * cy],
+                   [-sx * sz + cx * sy * cz, -cx * sy * sz - sx * cz, -cx * cy],
+                   [cx * cy * cz, -cx * cy * sz, cx * sy],
+                   [sx * cy * cz, -sx * cy * sz, sx * sy],
+                   [-sx * cz - cx * sy * sz, sx * sz - cx * sy * cz, 0],
+                   [cx * cz - sx * sy * sz, -sx * sy * cz - cx * sz, 0],
+                   [-cy * cz, cy * sz, -sy],
+                   [-sx * sy * cz, sx * sy * sz, sx * cy],
+                   [cx * sy * cz, -cx * sy * sz, -cx * cy],
+                   [sy * sz, sy * cz, 0],
+                   [-sx * cy * sz, -sx * cy * cz, 0],
+                   [cx * cy * sz, cx * cy * cz, 0],
+                   [-cy * cz, cy * sz, 0],
+                   [-cx * sz - sx * sy * cz, -cx * cz + sx * sy * sz, 0],
+                   [-sx * sz + cx * sy * cz, -cx * sy * sz - sx * cz, 0]])
+    return aj, ah
+
+
+# ---- neighbours ---------------------------------------------------------------------------------------------------------
+class CellSearch:
+    """target_cells_.radiusSearch(x', resolution): the centroids with float d2 < float(r * r), found among the 27 voxels
+    around the point (a centroid within r of the point differs from it by less than one voxel along every axis)."""
+    OFF = 1 << 20
+
+    def __init__(self, centroids, resolution):
+        self.c = np.ascontiguousarray(centroids, F)
+        self.inv = F(1.0) / F(resolution)
+        r = float(F(resolution))
+        self.r2 = F(r * r)
+        key = self._key(np.floor(self.c * self.inv).astype(np.int64))
+        self.order = np.argsort(key, kind="stable")
+        self.keys, self.first, self.count = np.unique(key[self.order], return_index=True, return_counts=True)
+        d = np.array([(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)], np.int64)
+        self.dkey = (d[:, 0] * (2 * self.OFF) + d[:, 1]) * (2 * self.OFF) + d[:, 2]
+        self.cache = {}
+
+    def _key(self, ijk):
+        return ((ijk[:, 0] + self.OFF) * (2 * self.OFF) + (ijk[:, 1] + self.OFF)) * (2 * self.OFF) + (ijk[:, 2] + self.OFF)
+
+    def pairs(self, tc):
+        """-> (point index, cell index) of every pair within the radius, by point."""
+        tc = np.asarray(tc, F)
+        fin = np.flatnonzero(np.isfinite(tc).all(1))
+        if len(fin) == 0 or len(self.c) == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64)
+        # the candidate cells of every occupied voxel of the points (its 27 neighbours), then of every point
+        uk, inv = np.unique(self._key(np.floor(tc[fin] * self.inv).astype(np.int64)), return_inverse=True)
+        q = (uk[:, None] + self.dkey[None, :]).ravel()
+        pos = np.minimum(np.searchsorted(self.keys, q), len(self.keys) - 1)
+        hit = np.flatnonzero(self.keys[pos] == q)
+        cnt = self.count[pos[hit]]
+        within = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        vcells = self.order[np.repeat(self.first[pos[hit]], cnt) + within]
+        vcount = np.bincount(np.repeat(hit // 27, cnt), minlength=len(uk))
+        voff = np.cumsum(vcount) - vcount
+        pc = vcount[inv]
+        pi = np.repeat(fin, pc)
+        ci = vcells[np.repeat(voff[inv], pc) + (np.arange(int(pc.sum())) - np.repeat(np.cumsum(pc) - pc, pc))]
+        d = tc[pi] - self.c[ci]
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        keep = d2 < self.r2
+        return pi[keep], ci[keep]
+
+
+# ---- the derivative pass ----------------------------------------------------------------------------------------------------
+def pair_terms(x, src, tc, pi, ci, means, icov, d1, d2):
+    """updateDerivatives (impl/ndt.hpp:448-495) for every pair: (score terms (P,), gradient terms (P, 6), Hessian terms
+    (P, 6, 6)); pairs that fail the guard of :467 are zero rows."""
+    aj, ah = angle_tables(x)
+    xo = src[pi, :3].astype(np.float64)
+    P = len(pi)
+    paj = xo @ aj.T
+    J = np.zeros((P, 3, 6))
+    J[:, 0, 0] = J[:, 1, 1] = J[:, 2, 2] = 1
+    J[:, 1, 3], J[:, 2, 3] = paj[:, 0], paj[:, 1]
+    J[:, 0, 4], J[:, 1, 4], J[:, 2, 4] = paj[:, 2], paj[:, 3], paj[:, 4]
+    J[:, 0, 5], J[:, 1, 5], J[:, 2, 5] = paj[:, 5], paj[:, 6], paj[:, 7]
+    xt = tc[pi].astype(np.float64) - means[ci]
+    Ci = icov[ci]
+    q = np.einsum("pij,pj->pi", Ci, xt)
+    with np.errstate(all="ignore"):
+        e = np.exp(-d2 * np.einsum("pi,pi->p", xt, q) / 2)
+    score = -d1 * e
+    e2 = d2 * e
+    bad = (e2 > 1) | (e2 < 0) | np.isnan(e2)
+    e3 = e2 * d1
+    score[bad] = 0
+    e3[bad] = 0
+    CJ = np.einsum("pij,pjk->pik", Ci, J)
+    a = np.einsum("pi,pik->pk", xt, CJ)
+    g = a * e3[:, None]
+    pah = xo @ ah.T
+    z = np.zeros(P)
+    va, vb, vc = np.stack([z, pah[:, 0], pah[:, 1]], 1), np.stack([z, pah[:, 2], pah[:, 3]], 1), np.stack([z, pah[:, 4], pah[:, 5]], 1)
+    vd, ve, vf = pah[:, 6:9], pah[:, 9:12], pah[:, 12:15]
+    second = np.zeros((P, 6, 6))
+    for (i, j), v in {(3, 3): va, (4, 3): vb, (5, 3): vc, (3, 4): vb, (4, 4): vd, (5, 4): ve, (3, 5): vc, (4, 5): ve,
+                      (5, 5): vf}.items():
+        second[:, i, j] = np.einsum("pi,pi->p", xt, np.einsum("pij,pj->pi", Ci, v))
+    H = e3[:, None, None] * ((-d2 * a[:, :, None] * a[:, None, :] + second) + np.einsum("pkj,pki->pij", J, CJ))
+    g[bad] = 0
+    H[bad] = 0
+    return score, g, H
+
+
+def derivative_sums(x, src, tc, pi, ci, means, icov, d1, d2, chunk=1 << 17):
+    """The sums of pair_terms over the pairs: the same per-pair arithmetic written out by component (icov symmetric:
+    x' C v = (C x') . v), the contractions over the pairs as matrix products -- no (P, 6, 6) arrays.  In chunks."""
+    aj, ah = angle_tables(x)
+    icov6 = np.ascontiguousarray(icov.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]])
+    s, g, H = 0.0, np.zeros(6), np.zeros((6, 6))
+    blocks = {(3, 3): (None, 0, 1), (3, 4): (None, 2, 3), (3, 5): (None, 4, 5), (4, 4): (6, 7, 8), (4, 5): (9, 10, 11),
+              (5, 5): (12, 13, 14)}
+    for b in range(0, len(pi), chunk):
+        p, c = pi[b:b + chunk], ci[b:b + chunk]
+        xo = src[p, :3].astype(np.float64)
+        P = len(p)
+        paj, pah = np.ascontiguousarray((xo @ aj.T).T), np.ascontiguousarray((xo @ ah.T).T)
+        x0, x1, x2 = np.ascontiguousarray((tc[p].astype(np.float64) - means[c]).T)
+        c00, c01, c02, c11, c12, c22 = np.ascontiguousarray(icov6[c].T)
+
+        def mul(v0, v1, v2):  # C v
+            return c00 * v0 + c01 * v1 + c02 * v2, c01 * v0 + c11 * v1 + c12 * v2, c02 * v0 + c12 * v1 + c22 * v2
+        q = mul(x0, x1, x2)
+        with np.errstate(all="ignore"):
+            e = np.exp(-d2 * (x0 * q[0] + x1 * q[1] + x2 * q[2]) / 2)
+        e2 = d2 * e
+        bad = (e2 > 1) | (e2 < 0) | np.isnan(e2)
+        e3 = np.where(bad, 0.0, e2 * d1)
+        s += np.where(bad, 0.0, -d1 * e).sum()
+        z, one = np.zeros(P), np.ones(P)
+        Jc = [(one, z, z), (z, one, z), (z, z, one), (z, paj[0], paj[1]), (paj[2], paj[3], paj[4]), (paj[5], paj[6], paj[7])]
+        CJc = [(c00, c01, c02), (c01, c11, c12), (c02, c12, c22)] + [mul(*Jc[k]) for k in (3, 4, 5)]
+        a = np.stack([x0 * v[0] + x1 * v[1] + x2 * v[2] for v in CJc], 1)
+        g += e3 @ a
+        H += (a * (-d2 * e3)[:, None]).T @ a
+        for k in range(3):
+            CJk = np.stack([v[k] for v in CJc], 1)
+            Jk = np.stack([v[k] for v in Jc], 1)
+            H += (CJk * e3[:, None]).T @ Jk  # H(i, j) += e3 J(k, j) CJ(k, i)
+        for (i, j), rows in blocks.items():
+            t = sum((0.0 if r is None else e3 @ (q[k] * pah[r])) for k, r in enumerate(rows))
+            H[i, j] += t
+            if i != j:
+                H[j, i] += t
+    return s, g, H
+
+
+# ---- More-Thuente -------------------------------------------------------------------------------------------------------------
+def update_interval(S, a_t, f_t, g_t):
+    if f_t > S["f_l"]:
+        S["a_u"], S["f_u"], S["g_u"] = a_t, f_t, g_t
+        return False
+    if g_t * (S["a_l"] - a_t) > 0:
+        S["a_l"], S["f_l"], S["g_l"] = a_t, f_t, g_t
+        return False
+    if g_t * (S["a_l"] - a_t) < 0:
+        S["a_u"], S["f_u"], S["g_u"] = S["a_l"], S["f_l"], S["g_l"]
+        S["a_l"], S["f_l"], S["g_l"] = a_t, f_t, g_t
+        return False
+    return True
+
+
+def trial_value(S, a_t, f_t, g_t):
+    a_l, f_l, g_l, a_u, f_u, g_u = S["a_l"], S["f_l"], S["g_l"], S["a_u"], S["f_u"], S["g_u"]
+    if a_t == a_l and a_t == a_u:
+        return a_t
+    if a_t == a_l:
+        case = 4
+    elif f_t > f_l:
+        case = 1
+    elif g_t * g_l < 0:
+        case = 2
+    elif abs(g_t) <= abs(g_l):
+        case = 3
+    else:
+        case = 4
+    with np.errstate(all="ignore"):
+        if case in (1, 2, 3):
+            z = np.float64(3 * (f_t - f_l)) / np.float64(a_t - a_l) - g_t - g_l
+            w = np.sqrt(np.float64(z * z - g_t * g_l))
+            a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w)
+        if case == 1:
+            a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - np.float64(f_l - f_t) / np.float64(a_l - a_t))
+            return float(a_c) if abs(a_c - a_l) < abs(a_q - a_l) else float(0.5 * (a_q + a_c))
+        if case == 2:
+            a_s = a_l - np.float64(a_l - a_t) / np.float64(g_l - g_t) * g_l
+            return float(a_c) if abs(a_c - a_t) >= abs(a_s - a_t) else float(a_s)
+        if case == 3:
+            a_s = a_l - np.float64(a_l - a_t) / np.float64(g_l - g_t) * g_l
+            nxt = float(a_c) if abs(a_c - a_t) < abs(a_s - a_t) else float(a_s)
+            lim = a_t + 0.66 * (a_u - a_t)
+            if a_t > a_l:
+                return nxt if nxt < lim else lim
+            return nxt if lim < nxt else lim
+        z = np.float64(3 * (f_t - f_u)) / np.float64(a_t - a_u) - g_t - g_u
+        w = np.sqrt(np.float64(z * z - g_t * g_u))
+        return float(a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w))
+
+
+def svd_solve(H, b):
+    """JacobiSVD(H).solve(b): singular values at or below 6 eps * the largest are dropped (Eigen's rank())."""
+    if not (np.isfinite(H).all() and np.isfinite(b).all()):
+        return np.full(6, np.nan)
+    U, s, Vt = np.linalg.svd(H)
+    keep = s > s.max() * 6 * np.finfo(np.float64).eps
+    y = np.zeros(6)
+    y[keep] = (U.T @ b)[keep] / s[keep]
+    return Vt.T @ y
+
+
+# ---- the registration ---------------------------------------------------------------------------------------------------------
+class NDT:
+    def __init__(self, tgt, src, resolution=1.0, step_size=0.1, outlier_ratio=0.55, transformation_epsilon=0.1,
+                 rotation_epsilon=0.0, max_iterations=35, min_points=6, mult=0.01, cells=None, perturb=0.0, seed=0):
+        self.res, self.step_size, self.eps, self.rot_eps, self.max_it = F(resolution), step_size, transformation_epsilon, \
+            rotation_epsilon, max_iterations
+        self.cells = cells if cells is not None else voxel_cells(tgt, resolution, min_points, mult)
+        self.search = CellSearch(self.cells["centroids"], resolution)
+        self.src = np.ascontiguousarray(src[:, :3], F)
+        self.d1, self.d2 = gauss_constants(resolution, outlier_ratio)
+        self.evals = 0
+        self.last_pairs = 0
+        self.perturb = perturb
+        self.rng = np.random.default_rng(seed)
+
+    def derivatives(self, T, x):
+        self.evals += 1
+        tc = transform_se3(T, self.src)
+        pi, ci = self.search.pairs(tc)
+        self.last_pairs = len(pi)
+        s, g, H = derivative_sums(x, self.src, tc, pi, ci, self.cells["means"], self.cells["icov"], self.d1, self.d2)
+        if self.perturb:
+            s *= 1 + self.perturb * self.rng.standard_normal()
+            g = g * (1 + self.perturb * self.rng.standard_normal(6))
+            H = H * (1 + self.perturb * self.rng.standard_normal((6, 6)))
+        return s, g, H
+
+    def step_length(self, x, step_dir, step_init, step_max, step_min, st):
+        phi_0 = -st["score"]
+        d_phi_0 = -(st["g"] @ step_dir)
+        if d_phi_0 >= 0:
+            if d_phi_0 == 0:
+                return 0.0, step_dir, 0
+            d_phi_0 *= -1
+            step_dir = -step_dir
+        mu, nu = 1e-4, 0.9
+        S = dict(a_l=0.0, a_u=0.0)
+        S["f_l"] = S["f_u"] = phi_0 - phi_0 - mu * d_phi_0 * 0.0
+        S["g_l"] = S["g_u"] = d_phi_0 - mu * d_phi_0
+        interval_converged = (step_max - step_min) < 0
+        open_interval = True
+        a_t = max(min(step_init, step_max), step_min)
+        x_t = x + step_dir * a_t
+        st["final"] = convert_transform(x_t)
+        st["score"], st["g"], st["H"] = self.derivatives(st["final"], x_t)
+        phi_t = -st["score"]
+        d_phi_t = -(st["g"] @ step_dir)
+        psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t
+        d_psi_t = d_phi_t - mu * d_phi_0
+        it = 0
+        while not interval_converged and it < 10 and (psi_t > 0 or d_phi_t > -nu * d_phi_0):
+            a_t = trial_value(S, a_t, psi_t, d_psi_t) if open_interval else trial_value(S, a_t, phi_t, d_phi_t)
+            a_t = max(min(a_t, step_max), step_min)
+            x_t = x + step_dir * a_t
+            st["final"] = convert_transform(x_t)
+            st["score"], st["g"], H_t = self.derivatives(st["final"], x_t)
+            phi_t = -st["score"]
+            d_phi_t = -(st["g"] @ step_dir)
+            psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t
+            d_psi_t = d_phi_t - mu * d_phi_0
+            if open_interval and psi_t <= 0 and d_psi_t >= 0:
+                open_interval = False
+                S["f_l"] += phi_0 - mu * d_phi_0 * S["a_l"]
+                S["g_l"] += mu * d_phi_0
+                S["f_u"] += phi_0 - mu * d_phi_0 * S["a_u"]
+                S["g_u"] += mu * d_phi_0
+            if open_interval:
+                interval_converged = update_interval(S, a_t, psi_t, d_psi_t)
+            else:
+                interval_converged = update_interval(S, a_t, phi_t, d_phi_t)
+            it += 1
+        if it:
+            st["H"] = H_t  # computeHessian at the accepted trial: the Hessian part of the same pass
+        return a_t, step_dir, it
+
+    def align(self, guess=None):
+        final = np.eye(4, dtype=F)
+        out = dict(T=final, nr_iterations=0, converged=False, steps=[], trials=[], score=0.0, evals=0)
+        if len(self.cells["npoints"]) == 0:
+            return out
+        if guess is not None and not np.array_equal(np.asarray(guess, F), final):
+            final = np.asarray(guess, F).copy()
+        x = euler_from(final)
+        st = dict(final=final)
+        st["score"], st["g"], st["H"] = self.derivatives(final, x)
+        nr, converged = 0, False
+        while not converged:
+            delta = svd_solve(st["H"], -st["g"])
+            dn = float(np.sqrt((delta * delta).sum()))
+            if dn == 0 or math.isnan(dn):
+                converged = dn == 0
+                break
+            delta = delta / dn
+            dn, delta, it = self.step_length(x, delta, dn, self.step_size, self.eps / 2, st)
+            delta = delta * dn
+            out["steps"].append(dn)
+            out["trials"].append(it)
+            Tm = convert_transform(delta)
+            x = x + delta
+            cos_angle = 0.5 * float((Tm[0, 0] + Tm[1, 1] + Tm[2, 2]) - F(1))
+            tsq = float((Tm[0, 3] * Tm[0, 3] + Tm[1, 3] * Tm[1, 3]) + Tm[2, 3] * Tm[2, 3])
+            nr += 1
+            te, re = self.eps, self.rot_eps
+            if (nr >= self.max_it or ((te > 0 and tsq <= te) and (re > 0 and cos_angle >= re)) or
+                    ((te <= 0) and (re > 0 and cos_angle >= re)) or ((te > 0 and tsq <= te) and re <= 0)):
+                converged = True
+        out.update(T=st["final"], nr_iterations=nr, converged=converged, score=st["score"], evals=self.evals, x=x)
+        return out
+
+
+def fitness(tgt, src, T):
+    """Registration::getFitnessScore: mean squared distance of the transformed source to its nearest target point."""
+    tc = transform_se3(T, src[:, :3]).astype(np.float64)
+    t = np.ascontiguousarray(tgt[:, :3], np.float64)
+    tot = 0.0
+    for b in range(0, len(tc), 256):
+        d = ((tc[b:b + 256, None, :] - t[None, :, :]) ** 2).sum(2)
+        tot += d.min(1).sum()
+    return tot / len(tc)
