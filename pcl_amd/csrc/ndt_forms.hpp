@@ -17,6 +17,11 @@
 //   * the cell's inverse covariance is kept as its 6 distinct entries, (i, j) from the upper triangle of cov^-1 computed
 //     by the symmetric cofactor form: the reference's full inverse of V L V^-1 is asymmetric by a few ulp
 //     (<= 1e-15 * max|icov|, cond <= 100 after the inflation);  V^-1 is taken as V^T (V orthogonal to 1e-16);
+//   * a cell that keeps its eigenvalues inverts the raw covariance of :326, which is not symmetric (see eig3_sym): the
+//     reference's inverse is then not symmetric either, and the 6 entries kept here are those of the inverse of the
+//     symmetrised matrix, its symmetric part to first order.  The part left out is eps * |mean|^2 / variance * cond:
+//     up to 2.9e-13 * max|icov| on cells 0.3 wide inside [-1, 1]^3, 1e-3 on a cell at 3e4.  x' C x does not see it;
+//     x' C J_i does (the gradient and Hessian terms of such a pair, by that relative amount);
 //   * the pair Hessian is accumulated for i <= j and mirrored: the reference's (i, j) and (j, i) differ only by the
 //     association of (-d2 a_i) a_j, one ulp of that term.
 #pragma once
@@ -141,12 +146,16 @@ PCLHIP_HD void angle_tables(const double x[6], NdtAngles& A) {
     for (int c = 0; c < 3; ++c) A.h[r][c] = H[r][c];
 }
 
-// Eigenvalues (ascending) and eigenvectors (columns of V, row-major) of a symmetric 3x3: cyclic Jacobi in double.
+// Eigenvalues (ascending) and eigenvectors (columns of V, row-major) of a symmetric 3x3: cyclic Jacobi in double.  Only
+// the lower triangle of Ain is read, as Eigen's SelfAdjointEigenSolver does (voxel_grid_covariance.hpp:329): the raw
+// covariance of :326 is not symmetric (pt_sum[r] * mean[c] against pt_sum[c] * mean[r]), and far from the origin the
+// two triangles decide the eigenvalue tests of a thin cell differently (sheet at (1e4, -1e4, 1e4), resolution 0.05: 2 of
+// 1912 validity flags; at 3e4: 4 of 1922).
 PCLHIP_HD void eig3_sym(const double Ain[9], double w[3], double V[9]) {
   double A[3][3], U[3][3];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {
-      A[i][j] = 0.5 * (Ain[3 * i + j] + Ain[3 * j + i]);
+      A[i][j] = i >= j ? Ain[3 * i + j] : Ain[3 * j + i];
       U[i][j] = i == j ? 1.0 : 0.0;
     }
   for (int sweep = 0; sweep < 40; ++sweep) {

@@ -176,7 +176,11 @@ DEFAULTS = dict(max_iterations=200, transformation_epsilon=5e-4, rotation_epsilo
 
 def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
     """computeTransformation (impl/gicp.hpp:768-930).  tgt, src: (n, >=3) float32.  Returns a dict with T (final),
-    nr_iterations, converged, per-iteration `correspondences`, `inner`, `f`, and the last pairs (src index, tgt index, M)."""
+    nr_iterations, converged, per-iteration `correspondences`, `inner`, `f`, and the last pairs (src index, tgt index, M).
+    Which branch of the line search every Newton step took: `alphas`, one list per outer iteration with the accepted
+    alpha of each step and -1 for a step on which none of the ten candidates lowered f (the inner loop ends there);
+    `first_step`: (x, delta, f) of the first Newton step of the last outer iteration, for tests that evaluate its
+    candidates one by one; `R`: the rotation of transformation_ * guess that the last pairs' M were built with."""
     P = dict(DEFAULTS, **params)
     tgt = np.ascontiguousarray(tgt[:, :3], F)
     src = np.ascontiguousarray(src[:, :3], F)
@@ -197,7 +201,7 @@ def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
     Tk = np.eye(4, dtype=F)
     Tprev = Tk.copy()
     nr, converged = 0, False
-    out = dict(correspondences=[], inner=[], f=[])
+    out = dict(correspondences=[], inner=[], f=[], alphas=[])
     md2 = P["max_correspondence_distance"] ** 2
     while not converged:
         R = (Tk.astype(np.float64) @ guess.astype(np.float64))[:3, :3]
@@ -212,6 +216,7 @@ def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
         mahal[si[upd]] = inv[upd]
         Tprev = Tk.copy()
         out["pairs"] = (si, ti, mahal[si].copy())
+        out["R"] = R  # the rotation the source covariances of these pairs were turned by
         if len(si) < P["min_number_correspondences"]:
             break
         p, q, M = output[si], tgt[ti], mahal[si]
@@ -219,9 +224,12 @@ def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
         f = functor(x, p, q, M)
         _, g, H = dfddf(x, p, q, M)
         inner = 0
+        alphas = []
         while True:
             inner += 1
             delta = newton_step(H, g)
+            if inner == 1:
+                out["first_step"] = (x.copy(), delta.copy(), f)
             alpha, found = 1.0, False
             for _ in range(10):
                 cx = x - alpha * delta
@@ -230,6 +238,7 @@ def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
                     x, f, found = cx, cf, True
                     break
                 alpha /= 2
+            alphas.append(alpha if found else -1.0)
             if not found:
                 break
             _, g, H = dfddf(x, p, q, M)
@@ -245,6 +254,7 @@ def gicp_align(orc, tgt, src, guess=None, src_cov=None, tgt_cov=None, **params):
         nr += 1
         out["correspondences"].append(len(si))
         out["inner"].append(inner)
+        out["alphas"].append(alphas)
         out["f"].append(f)
         if nr >= P["max_iterations"] or delta_T < 1:
             converged = True

@@ -319,20 +319,27 @@ def update_interval(S, a_t, f_t, g_t):
     return True
 
 
+def trial_case(S, a_t, f_t, g_t):
+    """The branch trial_value takes: 1-4 (trialValueSelectionMT's cases), 0 for its early return."""
+    a_l, f_l, g_l, a_u = S["a_l"], S["f_l"], S["g_l"], S["a_u"]
+    if a_t == a_l and a_t == a_u:
+        return 0
+    if a_t == a_l:
+        return 4
+    if f_t > f_l:
+        return 1
+    if g_t * g_l < 0:
+        return 2
+    if abs(g_t) <= abs(g_l):
+        return 3
+    return 4
+
+
 def trial_value(S, a_t, f_t, g_t):
     a_l, f_l, g_l, a_u, f_u, g_u = S["a_l"], S["f_l"], S["g_l"], S["a_u"], S["f_u"], S["g_u"]
-    if a_t == a_l and a_t == a_u:
+    case = trial_case(S, a_t, f_t, g_t)
+    if case == 0:
         return a_t
-    if a_t == a_l:
-        case = 4
-    elif f_t > f_l:
-        case = 1
-    elif g_t * g_l < 0:
-        case = 2
-    elif abs(g_t) <= abs(g_l):
-        case = 3
-    else:
-        case = 4
     with np.errstate(all="ignore"):
         if case in (1, 2, 3):
             z = np.float64(3 * (f_t - f_l)) / np.float64(a_t - a_l) - g_t - g_l
@@ -381,6 +388,7 @@ class NDT:
         self.last_pairs = 0
         self.perturb = perturb
         self.rng = np.random.default_rng(seed)
+        self.mt = []  # per line search: dict(cases (trial_value's branch per trial), closed (the interval closed), flipped)
 
     def derivatives(self, T, x):
         self.evals += 1
@@ -397,11 +405,14 @@ class NDT:
     def step_length(self, x, step_dir, step_init, step_max, step_min, st):
         phi_0 = -st["score"]
         d_phi_0 = -(st["g"] @ step_dir)
+        log = dict(cases=[], closed=False, flipped=False)
+        self.mt.append(log)
         if d_phi_0 >= 0:
             if d_phi_0 == 0:
                 return 0.0, step_dir, 0
             d_phi_0 *= -1
             step_dir = -step_dir
+            log["flipped"] = True
         mu, nu = 1e-4, 0.9
         S = dict(a_l=0.0, a_u=0.0)
         S["f_l"] = S["f_u"] = phi_0 - phi_0 - mu * d_phi_0 * 0.0
@@ -418,6 +429,7 @@ class NDT:
         d_psi_t = d_phi_t - mu * d_phi_0
         it = 0
         while not interval_converged and it < 10 and (psi_t > 0 or d_phi_t > -nu * d_phi_0):
+            log["cases"].append(trial_case(S, a_t, psi_t, d_psi_t) if open_interval else trial_case(S, a_t, phi_t, d_phi_t))
             a_t = trial_value(S, a_t, psi_t, d_psi_t) if open_interval else trial_value(S, a_t, phi_t, d_phi_t)
             a_t = max(min(a_t, step_max), step_min)
             x_t = x + step_dir * a_t
@@ -429,6 +441,7 @@ class NDT:
             d_psi_t = d_phi_t - mu * d_phi_0
             if open_interval and psi_t <= 0 and d_psi_t >= 0:
                 open_interval = False
+                log["closed"] = True
                 S["f_l"] += phi_0 - mu * d_phi_0 * S["a_l"]
                 S["g_l"] += mu * d_phi_0
                 S["f_u"] += phi_0 - mu * d_phi_0 * S["a_u"]
@@ -473,7 +486,7 @@ class NDT:
             if (nr >= self.max_it or ((te > 0 and tsq <= te) and (re > 0 and cos_angle >= re)) or
                     ((te <= 0) and (re > 0 and cos_angle >= re)) or ((te > 0 and tsq <= te) and re <= 0)):
                 converged = True
-        out.update(T=st["final"], nr_iterations=nr, converged=converged, score=st["score"], evals=self.evals, x=x)
+        out.update(T=st["final"], nr_iterations=nr, converged=converged, score=st["score"], evals=self.evals, x=x, mt=self.mt)
         return out
 
 

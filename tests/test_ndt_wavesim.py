@@ -1,7 +1,8 @@
-"""NormalDistributionsTransform's kernels in the CPU tier: the `-m gpu` tests of tests/test_gpu_ndt.py and the C++ mirror's
-bunny test (tests/test_gpu_ndt_cpp.py) run on the wavefront emulation of tests/wavesim (the recipe of
-tests/test_gicp_wavesim.py: PCLHIP_LIB = the emulation, PCLHIP_ALLOW_WAVESIM=1, in a subprocess), at the bunny and, for the
-synthetic pair, 2^15-point sizes (tests/test_gpu_ndt.py: SYNTH_N); the 10M-point alignment stays on the GPU."""
+"""NormalDistributionsTransform's kernels in the CPU tier: the `-m gpu` tests of tests/test_gpu_ndt.py, of
+tests/test_gpu_ndt_regimes.py and the C++ mirror's bunny test (tests/test_gpu_ndt_cpp.py) run on the wavefront emulation
+of tests/wavesim (the recipe of tests/test_gicp_wavesim.py: PCLHIP_LIB = the emulation, PCLHIP_ALLOW_WAVESIM=1, in a
+subprocess), at the bunny and, for the synthetic pair, 2^15-point sizes (tests/test_gpu_ndt.py: SYNTH_N); the 10M-point
+alignment stays on the GPU."""
 import os
 import shutil
 import subprocess
@@ -26,7 +27,8 @@ def wavesim_lib():
 def test_ndt_gpu_tests_on_the_emulation(wavesim_lib):
     env = dict(os.environ, PCLHIP_LIB=wavesim_lib, PCLHIP_ALLOW_WAVESIM="1")
     cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", "not 10m",
-           os.path.join(ROOT, "tests", "test_gpu_ndt.py"), os.path.join(ROOT, "tests", "test_gpu_ndt_cpp.py")]
+           os.path.join(ROOT, "tests", "test_gpu_ndt.py"), os.path.join(ROOT, "tests", "test_gpu_ndt_cpp.py"),
+           os.path.join(ROOT, "tests", "test_gpu_ndt_regimes.py")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
     tail = r.stdout[-3000:] + "\n" + r.stderr[-3000:]
     assert r.returncode == 0, tail
