@@ -11,12 +11,13 @@
 //   Newton      gicp_eval_kernel<10>: f at all ten line-search candidates x - 2^-j delta, and the 12 gradient sums at
 //               alpha = 1; gicp_eval_kernel<1> (the gradient pass) only when a smaller alpha wins, or for x0
 // Every pass streams the pair records once; the serial part (Hessian assembly, 6x6 eigen-solve, alpha, the gradient and
-// delta tests: gicp_forms.hpp) runs on the host between passes.  Sums: per thread in a fixed order, wave / block trees,
-// then one row per block, the rows summed in a fixed order by gicp_finalize_kernel -- no atomics: two runs give the same bits.
+// delta tests: gicp_forms.hpp) runs on the host between passes.  Sums: per thread in a fixed order, then the fixed-order
+// block sums of block_sums.hpp (rows of 64 doubles).
 #pragma once
 
 #include <chrono>
 
+#include "block_sums.hpp"
 #include "gicp_forms.hpp"
 
 struct pclhip_gicp {
@@ -30,10 +31,7 @@ struct pclhip_gicp {
   float4* moved = nullptr;             // [icp->n] the source moved by the guess, slot order
   double* mstore = nullptr;            // [icp->n * 6] Mahalanobis matrix per source slot (mahalanobis_)
   void* pairs = nullptr;               // [icp->n] GicpPair
-  double* partials = nullptr;          // [blocks * 64]
-  double* sums_dev = nullptr;          // [64]
-  double* sums_host = nullptr;         // pinned [64]
-  int blocks = 0;
+  pclhip::BlockSums<64> sums;          // rows of the pack / evaluation passes
   bool have_pairs = false;
   double cached[pclhip::gf::kGicpCached] = {};  // of the last outer iteration
   pclhip_gicp_trace* trace = nullptr;
@@ -72,25 +70,6 @@ __global__ __launch_bounds__(BLOCK) void gicp_move_kernel(const float4* __restri
   o.w = p.w;
   moved[i] = o;
   cur[i] = o;
-}
-
-// one row of NS block sums per block (wave trees, then the block's waves in order)
-template <int NS>
-__device__ __forceinline__ void gicp_block_rows(const double (&acc)[NS], double* __restrict__ partials) {
-  __shared__ double red_s[WAVES_PER_BLOCK][NS];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const double v = wave_sum_d(acc[s]);
-    if (lane == 0) red_s[wave][s] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double a = 0.0;
-#pragma unroll
-    for (int w = 0; w < WAVES_PER_BLOCK; ++w) a += red_s[w][threadIdx.x];
-    partials[size_t(blockIdx.x) * 64 + threadIdx.x] = a;
-  }
 }
 
 // the pairs of an outer iteration (impl/gicp.hpp:858-876) and the x-independent sums of dfddf (:660-679)
@@ -163,7 +142,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_pack_kernel(IndexView ix, const fl
 #pragma unroll
       for (int k = 0; k < 6; ++k) acc[25 + 6 * l + k] += m[k] * pp[l];
   }
-  gicp_block_rows<gf::kGicpCached>(acc, partials);
+  block_rows<gf::kGicpCached, WAVES_PER_BLOCK, 64>(acc, partials);
 }
 
 // f at NC transforms and, for the first, the 12 gradient sums (OptimizationFunctorWithIndices, impl/gicp.hpp:480-640):
@@ -203,18 +182,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_eval_kernel(const GicpPair* __rest
       }
     }
   }
-  gicp_block_rows<NS>(acc, partials);
-}
-
-// the block rows summed in a fixed order: one wave per sum, lane l adds rows l, l + 64, ... (coalesced across the
-// sums' waves), then the wave's tree
-__global__ __launch_bounds__(WAVE) void gicp_finalize_kernel(const double* __restrict__ partials, int blocks,
-                                                             double* __restrict__ out) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  double a = 0.0;
-  for (int b = lane; b < blocks; b += WAVE) a += partials[size_t(b) * 64 + s];
-  a = wave_sum_d(a);
-  if (lane == 0) out[s] = a;
+  block_rows<NS, WAVES_PER_BLOCK, 64>(acc, partials);
 }
 
 __global__ void gicp_scatter_cov_kernel(const float4* __restrict__ pts, uint32_t n, const double* __restrict__ cov_sorted,
@@ -242,23 +210,6 @@ __global__ void gicp_fetch_m_kernel(const float4* __restrict__ moved, uint32_t n
 
 namespace {
 
-pclhip_status gicp_sums(pclhip_gicp* G, int ns, double* out) {
-  pclhip_ctx* ctx = G->ctx;
-  hipLaunchKernelGGL(gicp_finalize_kernel, dim3(ns), dim3(WAVE), 0, ctx->stream, G->partials, G->blocks, G->sums_dev);
-  PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-  (void)hipEventRecord(G->ev_b, ctx->stream);
-  PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(G->sums_host, G->sums_dev, size_t(ns) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(out, G->sums_host, size_t(ns) * sizeof(double));
-  return PCLHIP_OK;
-}
-
-Mat34 mat34_of(const float T[16]) {
-  Mat34 m;
-  for (int k = 0; k < 12; ++k) m.m[k] = T[k];
-  return m;
-}
-
 // f at x - 2^-j delta for j < nc (nc = 1: at x itself) + the gradient sums at the first; out: nc + 12 doubles
 pclhip_status gicp_eval(pclhip_gicp* G, int nc, const double (*xs)[6], double* out) {
   pclhip_ctx* ctx = G->ctx;
@@ -271,14 +222,14 @@ pclhip_status gicp_eval(pclhip_gicp* G, int nc, const double (*xs)[6], double* o
   const uint32_t n = G->icp->n;
   (void)hipEventRecord(G->ev_a, ctx->stream);
   if (nc == 1)
-    hipLaunchKernelGGL(gicp_eval_kernel<1>, dim3(G->blocks), dim3(BLOCK), 0, ctx->stream,
-                       static_cast<const GicpPair*>(G->pairs), n, X, G->partials);
+    hipLaunchKernelGGL(gicp_eval_kernel<1>, dim3(G->sums.blocks), dim3(BLOCK), 0, ctx->stream,
+                       static_cast<const GicpPair*>(G->pairs), n, X, G->sums.partials);
   else
-    hipLaunchKernelGGL(gicp_eval_kernel<gf::kGicpCandidates>, dim3(G->blocks), dim3(BLOCK), 0, ctx->stream,
-                       static_cast<const GicpPair*>(G->pairs), n, X, G->partials);
+    hipLaunchKernelGGL(gicp_eval_kernel<gf::kGicpCandidates>, dim3(G->sums.blocks), dim3(BLOCK), 0, ctx->stream,
+                       static_cast<const GicpPair*>(G->pairs), n, X, G->sums.partials);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   ++G->passes;
-  const pclhip_status st = gicp_sums(G, nc + 12, out);  // (synchronises: the pass's events are complete)
+  const pclhip_status st = G->sums.read(ctx, nc + 12, out, G->ev_b);  // (synchronises: the pass's events are complete)
   float ms = 0;
   if (st == PCLHIP_OK && hipEventElapsedTime(&ms, G->ev_a, G->ev_b) == hipSuccess) G->eval_ms += ms;
   return st;
@@ -295,30 +246,23 @@ pclhip_status gicp_dfddf(pclhip_gicp* G, const double x[6], double* f, double g[
   return PCLHIP_OK;
 }
 
-void free_dev(pclhip_ctx* ctx, void* p) {
-  if (p) dev_free(ctx, p);
-}
-
 pclhip_status gicp_alloc_source_state(pclhip_gicp* G) {
   pclhip_ctx* ctx = G->ctx;
   const uint32_t n = G->icp->n;
-  free_dev(ctx, G->moved);
-  free_dev(ctx, G->mstore);
-  free_dev(ctx, G->pairs);
-  free_dev(ctx, G->partials);
+  dev_free_if(ctx, G->moved);
+  dev_free_if(ctx, G->mstore);
+  dev_free_if(ctx, G->pairs);
   G->moved = nullptr;
   G->mstore = nullptr;
   G->pairs = nullptr;
-  G->partials = nullptr;
   const size_t nn = n ? n : 1;
   int blocks = int((uint64_t(n) + BLOCK - 1) / BLOCK);
   if (blocks > ctx->num_cus * 4) blocks = ctx->num_cus * 4;  // four workgroups (four waves per SIMD) per CU
   if (blocks < 1) blocks = 1;
-  G->blocks = blocks;
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &G->moved, nn * sizeof(float4)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &G->mstore, nn * 6 * sizeof(double)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &G->pairs, nn * sizeof(GicpPair)));
-  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &G->partials, size_t(blocks) * 64 * sizeof(double)));
+  PCLHIP_CHECK_HIP(ctx, G->sums.resize(ctx, blocks));
   // mahalanobis_.resize(N, Identity) (impl/gicp.hpp:773)
   std::vector<double> ident(nn * 6);
   for (size_t i = 0; i < nn; ++i) {
@@ -361,15 +305,13 @@ pclhip_status gicp_index_covariances(pclhip_index* ix, int k, double eps, uint64
 
 pclhip_status gicp_user_covariances(pclhip_gicp* G, const double* cov, uint64_t n, double** slot) {
   pclhip_ctx* ctx = G->ctx;
-  free_dev(ctx, *slot);
+  dev_free_if(ctx, *slot);
   *slot = nullptr;
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, slot, size_t(n ? n : 1) * 9 * sizeof(double)));
   PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(*slot, cov, size_t(n) * 9 * sizeof(double), hipMemcpyDefault, ctx->stream));
   PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PCLHIP_OK;
 }
-
-const float kIdent16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 }  // namespace
 }  // namespace pclhip
@@ -406,9 +348,7 @@ pclhip_status pclhip_gicp_create(pclhip_index* target, pclhip_gicp** out) {
   G->icp = icp;
   icp->order_override = 1;   // transformPointCloud: Transformer order
   icp->search_only = true;   // the GICP passes replace the ICP accumulation
-  if (dev_malloc(ctx, &G->sums_dev, 64 * sizeof(double)) != hipSuccess ||
-      pinned_malloc(ctx, &G->sums_host, 64 * sizeof(double)) != hipSuccess ||
-      hipEventCreate(&G->ev_a) != hipSuccess || hipEventCreate(&G->ev_b) != hipSuccess) {
+  if (G->sums.create(ctx) != hipSuccess || hipEventCreate(&G->ev_a) != hipSuccess || hipEventCreate(&G->ev_b) != hipSuccess) {
     set_error(ctx, "allocation failed in pclhip_gicp_create");
     pclhip_gicp_destroy(G);
     return PCLHIP_ERR_HIP;
@@ -421,16 +361,14 @@ void pclhip_gicp_destroy(pclhip_gicp* G) {
   if (!G) return;
   pclhip_ctx* ctx = G->ctx;
   (void)hipStreamSynchronize(ctx->stream);
-  free_dev(ctx, G->src_cov);
-  free_dev(ctx, G->tgt_cov);
-  free_dev(ctx, G->moved);
-  free_dev(ctx, G->mstore);
-  free_dev(ctx, G->pairs);
-  free_dev(ctx, G->partials);
-  free_dev(ctx, G->sums_dev);
+  dev_free_if(ctx, G->src_cov);
+  dev_free_if(ctx, G->tgt_cov);
+  dev_free_if(ctx, G->moved);
+  dev_free_if(ctx, G->mstore);
+  dev_free_if(ctx, G->pairs);
+  G->sums.release(ctx);
   if (G->ev_a) (void)hipEventDestroy(G->ev_a);
   if (G->ev_b) (void)hipEventDestroy(G->ev_b);
-  if (G->sums_host) pinned_free(ctx, G->sums_host, 64 * sizeof(double));
   if (G->icp) pclhip_icp_destroy(G->icp);
   delete G;
 }
@@ -442,7 +380,7 @@ pclhip_status pclhip_gicp_set_source(pclhip_gicp* G, const void* points, size_t 
   pclhip_status st = pclhip_icp_set_source(G->icp, points, stride_bytes, n);
   if (st != PCLHIP_OK) return st;
   G->n_src_orig = n;
-  free_dev(ctx, G->src_cov);  // setInputSource drops the source covariances (gicp.h:160-166)
+  dev_free_if(ctx, G->src_cov);  // setInputSource drops the source covariances (gicp.h:160-166)
   G->src_cov = nullptr;
   G->src_cov_user = false;
   return gicp_alloc_source_state(G);
@@ -483,7 +421,7 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
                  "invalid GICP parameters");
   PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   std::memset(res, 0, sizeof *res);
-  const float* guess = guess_in ? guess_in : kIdent16;
+  const float* guess = guess_in ? guess_in : kIdentity16;
   const auto t0 = std::chrono::steady_clock::now();
   // covariances once, cached (:775-784)
   double cov_ms = 0.0;
@@ -493,7 +431,7 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
       PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &G->tgt_cov, size_t(G->target->n_orig ? G->target->n_orig : 1) * 9 * sizeof(double)));
       pclhip_status st = gicp_index_covariances(G->target, P->k_correspondences, P->gicp_epsilon, G->target->n_orig, G->tgt_cov);
       if (st != PCLHIP_OK) {
-        free_dev(ctx, G->tgt_cov);
+        dev_free_if(ctx, G->tgt_cov);
         G->tgt_cov = nullptr;
         return st;
       }
@@ -506,7 +444,7 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
       st = gicp_index_covariances(six, P->k_correspondences, P->gicp_epsilon, G->n_src_orig, G->src_cov);
       pclhip_index_destroy(six);
       if (st != PCLHIP_OK) {
-        free_dev(ctx, G->src_cov);
+        dev_free_if(ctx, G->src_cov);
         G->src_cov = nullptr;
         return st;
       }
@@ -530,8 +468,8 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
     if (double(fmax2) > md2) fmax2 = std::nextafterf(fmax2, 0.0f);
   }
   float Tk[16], Tprev[16];
-  std::memcpy(Tk, kIdent16, sizeof Tk);
-  std::memcpy(Tprev, kIdent16, sizeof Tprev);
+  std::memcpy(Tk, kIdentity16, sizeof Tk);
+  std::memcpy(Tprev, kIdentity16, sizeof Tprev);
   int nr = 0, newton_total = 0, alpha_one = 0, steps = 0, ntrace = 0;
   bool converged = false;
   uint64_t last_m = 0;
@@ -553,11 +491,11 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
     if (st != PCLHIP_OK) return st;
     if (n > 0) {
       (void)hipEventRecord(G->ev_a, ctx->stream);
-      hipLaunchKernelGGL(gicp_pack_kernel, dim3(G->blocks), dim3(BLOCK), 0, ctx->stream, G->target->view(), G->moved, n,
+      hipLaunchKernelGGL(gicp_pack_kernel, dim3(G->sums.blocks), dim3(BLOCK), 0, ctx->stream, G->target->view(), G->moved, n,
                          icp->match_pos, icp->match, G->src_cov, G->tgt_cov, R, G->mstore, static_cast<GicpPair*>(G->pairs),
-                         G->partials);
+                         G->sums.partials);
       PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-      st = gicp_sums(G, gf::kGicpCached, G->cached);
+      st = G->sums.read(ctx, gf::kGicpCached, G->cached, G->ev_b);
       if (st != PCLHIP_OK) return st;
       float pms = 0;
       if (hipEventElapsedTime(&pms, G->ev_a, G->ev_b) == hipSuccess) G->pack_ms += pms;

@@ -337,19 +337,17 @@ void fill_criteria(const pclhip_icp_params* p, cf::Criteria& c) {  // impl/icp.h
   c.mse_threshold_absolute = p->mse_threshold_absolute;
 }
 
-const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-
 // upload the control block: an alignment starts with the next launch
 pclhip_status arm_loop(pclhip_icp* icp, const pclhip_icp_params* p, const float* guess, bool auto_restart) {
   pclhip_ctx* ctx = icp->ctx;
   PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // nothing of a previous loop is still reading the staging copy
   IcpControl& c = *icp->ctl_host;
   std::memset(&c, 0, sizeof c);
-  const float* g = guess ? guess : kIdentity;
+  const float* g = guess ? guess : kIdentity16;
   std::memcpy(c.guess, g, sizeof c.guess);
   std::memcpy(c.final_T, g, sizeof c.final_T);  // icp.hpp:123
   std::memcpy(c.T_apply, g, sizeof c.T_apply);  // :126-131, applied by the first launch
-  std::memcpy(c.Tk, kIdentity, sizeof c.Tk);
+  std::memcpy(c.Tk, kIdentity16, sizeof c.Tk);
   c.restart = 1;
   c.stop = 0;
   c.mode = p->mode;
@@ -440,8 +438,8 @@ pclhip_status icp_align_device(pclhip_icp* icp, const pclhip_icp_params* params,
   if (st != PCLHIP_OK) return st;
   st = arm_loop(icp, params, guess, false);
   if (st != PCLHIP_OK) return st;
-  std::memcpy(res->final_transformation, guess ? guess : kIdentity, sizeof res->final_transformation);
-  std::memcpy(res->last_transformation, kIdentity, sizeof res->last_transformation);
+  std::memcpy(res->final_transformation, guess ? guess : kIdentity16, sizeof res->final_transformation);
+  std::memcpy(res->last_transformation, kIdentity16, sizeof res->last_transformation);
   double search_ms = 0, total_ms = 0;
   st = run_loop(icp, params, loop_window(icp->ctx), -1, [&](const IcpStepRecord& r, const StepTimes& t) {
     search_ms += t.kernels_ms;

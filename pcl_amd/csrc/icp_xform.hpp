@@ -8,6 +8,11 @@ namespace pclhip {
 struct Mat34 {
   float m[12];  // rows 0..2 of the 4x4
 };
+inline Mat34 mat34_of(const float T[16]) {
+  Mat34 m;
+  for (int k = 0; k < 12; ++k) m.m[k] = T[k];
+  return m;
+}
 
 // order 0: Eigen Matrix4f * Vector4f (registration/include/pcl/registration/impl/icp.hpp:49-111)
 // order 1: Transformer<float>::se3 (common/include/pcl/common/impl/transforms.hpp:117-123)

@@ -13,16 +13,16 @@
 //                           pair loop.  Three variants as the reference has them: <1,1> score + gradient + Hessian,
 //                           <1,0> the line search's trials, <0,1> computeHessian.
 //   sums                    per thread in traversal order over a FIXED share of the groups (GroupSchedule without the
-//                           dynamic tail: which wave serves which group does not depend on timing), wave trees, the
-//                           block's waves in order, one row per block; ndt_finalize_kernel adds the rows in a fixed
-//                           order.  No atomics: two runs give the same bits, and a variant gives the bits of the full
-//                           pass for its part.
+//                           dynamic tail: which wave serves which group does not depend on timing), then the
+//                           fixed-order block sums of block_sums.hpp (rows of 32 doubles): a variant gives the bits of
+//                           the full pass for its part.
 // The serial step (6x6 SVD solve, More-Thuente, convergence test: ndt_forms.hpp, host_math.cpp) runs on the host between
 // passes: one read-back of the sums per evaluation, nothing else crosses.
 #pragma once
 
 #include <chrono>
 
+#include "block_sums.hpp"
 #include "icp_xform.hpp"
 #include "ndt_forms.hpp"
 #include "traverse.hpp"
@@ -47,10 +47,7 @@ struct pclhip_ndt {
   float4* src_sorted = nullptr;
   // evaluation state
   uint32_t* lists = nullptr;    // [NDT_LIST_CAP][blocks * NDT_BLOCK]
-  double* partials = nullptr;   // [blocks * 32]
-  double* sums_dev = nullptr;   // [32]
-  double* sums_host = nullptr;  // pinned [32]
-  int blocks = 0;
+  pclhip::BlockSums<32> sums;   // (NDT_ROW) rows of an evaluation; sums.blocks is the evaluation's grid
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   int evals[3] = {0, 0, 0};     // full, gradient, Hessian passes of the last align
   double eval_ms[3] = {0, 0, 0};
@@ -71,7 +68,8 @@ constexpr int NDT_BLOCK = 256;
 constexpr int NDT_WAVES = NDT_BLOCK / WAVE;
 constexpr int NDT_LIST_CAP = 32;
 constexpr int NDT_NS = nf::kNdtSums + 1;  // + the number of points whose list overflowed (must be 0)
-constexpr int NDT_ROW = 32;               // doubles per block row
+constexpr int NDT_ROW = 32;               // doubles per block row (pclhip_ndt::sums)
+static_assert(NDT_NS <= NDT_ROW, "a row holds every sum");
 
 // collects the cells within the radius: l[3 * LEAF + j] is the centroid's position among the cells
 struct NdtCollect {
@@ -146,36 +144,16 @@ __global__ __launch_bounds__(NDT_BLOCK, 2) void ndt_eval_kernel(IndexView ix, co
       nf::pair_terms<WITH_G, WITH_H>(x, xt, C, A, d1, d2, acc);
     }
   }
-  // one row of block sums: wave trees, then the block's waves in order
+  // The wave step of block_sums.hpp, written out (red_s is touched behind the walk only).  Through wave_rows the helper's
+  // loop is unrolled before it is inlined here, and the register allocation of this kernel moves with it: <1,1> 248 -> 250
+  // VGPRs, <0,1> 238 -> 237, the accumulators' copies in another place.
 #pragma unroll
   for (int s = 0; s < NDT_NS; ++s) {
     const double v = wave_sum_d(acc[s]);
     if (lane == 0) red_s[wave][s] = v;
   }
-  __syncthreads();
-  if (threadIdx.x < NDT_NS) {
-    double a = 0.0;
-#pragma unroll
-    for (int w = 0; w < NDT_WAVES; ++w) a += red_s[w][threadIdx.x];
-    partials[size_t(blockIdx.x) * NDT_ROW + threadIdx.x] = a;
-  }
+  block_store<NDT_NS, NDT_WAVES, NDT_ROW>(red_s, partials);
 }
-
-// the block rows in a fixed order: one wave per sum, lane l adds rows l, l + 64, ..., then the wave's tree
-__global__ __launch_bounds__(WAVE) void ndt_finalize_kernel(const double* __restrict__ partials, int blocks,
-                                                            double* __restrict__ out) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  double a = 0.0;
-  for (int b = lane; b < blocks; b += WAVE) a += partials[size_t(b) * NDT_ROW + s];
-  a = wave_sum_d(a);
-  if (lane == 0) out[s] = a;
-}
-
-void ndt_free(pclhip_ctx* ctx, void* p) {
-  if (p) dev_free(ctx, p);
-}
-
-const float kNdtIdent[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 void ndt_drop_fitness(pclhip_ndt* N, bool target_too) {
   if (N->icp) {
@@ -238,29 +216,24 @@ pclhip_status ndt_eval(pclhip_ndt* N, const pclhip_ndt_params* P, int variant, c
   ++N->evals[variant];
   const uint32_t n = uint32_t(N->src_n);
   if (n == 0 || N->cells.count == 0) return PCLHIP_OK;
-  Mat34 M;
-  for (int k = 0; k < 12; ++k) M.m[k] = T[k];
+  const Mat34 M = mat34_of(T);
   const double rr = double(P->resolution) * double(P->resolution);
   const float r2 = float(rr);  // kdtree_flann.hpp:398
   const IndexView v = N->cell_index->view();
-  const dim3 grid(N->blocks), block(NDT_BLOCK);
+  const dim3 grid(N->sums.blocks), block(NDT_BLOCK);
   (void)hipEventRecord(N->ev_a, ctx->stream);
   if (variant == 0)
     hipLaunchKernelGGL((ndt_eval_kernel<true, true>), grid, block, 0, ctx->stream, v, N->src_sorted, n, M, r2, N->cells.rec,
-                       N->cells.count, A, d1, d2, N->lists, N->partials);
+                       N->cells.count, A, d1, d2, N->lists, N->sums.partials);
   else if (variant == 1)
     hipLaunchKernelGGL((ndt_eval_kernel<true, false>), grid, block, 0, ctx->stream, v, N->src_sorted, n, M, r2, N->cells.rec,
-                       N->cells.count, A, d1, d2, N->lists, N->partials);
+                       N->cells.count, A, d1, d2, N->lists, N->sums.partials);
   else
     hipLaunchKernelGGL((ndt_eval_kernel<false, true>), grid, block, 0, ctx->stream, v, N->src_sorted, n, M, r2, N->cells.rec,
-                       N->cells.count, A, d1, d2, N->lists, N->partials);
+                       N->cells.count, A, d1, d2, N->lists, N->sums.partials);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(ndt_finalize_kernel, dim3(NDT_NS), dim3(WAVE), 0, ctx->stream, N->partials, N->blocks, N->sums_dev);
-  PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-  (void)hipEventRecord(N->ev_b, ctx->stream);
-  PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(N->sums_host, N->sums_dev, NDT_NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(out, N->sums_host, NDT_NS * sizeof(double));
+  const pclhip_status st = N->sums.read(ctx, NDT_NS, out, N->ev_b);
+  if (st != PCLHIP_OK) return st;
   float ms = 0;
   if (hipEventElapsedTime(&ms, N->ev_a, N->ev_b) == hipSuccess) N->eval_ms[variant] += ms;
   if (out[NDT_NS - 1] != 0.0) {
@@ -364,7 +337,7 @@ pclhip_status ndt_step_length(pclhip_ndt* N, const pclhip_ndt_params* P, double 
 }
 
 pclhip_status ndt_copy_records(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, void** dst) {
-  ndt_free(ctx, *dst);
+  dev_free_if(ctx, *dst);
   *dst = nullptr;
   if (n == 0) return PCLHIP_OK;
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, dst, size_t(n) * stride));
@@ -398,9 +371,7 @@ pclhip_status pclhip_ndt_create(pclhip_ctx* ctx, pclhip_ndt** out) {
   PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   pclhip_ndt* N = new pclhip_ndt();
   N->ctx = ctx;
-  if (dev_malloc(ctx, &N->sums_dev, NDT_ROW * sizeof(double)) != hipSuccess ||
-      pinned_malloc(ctx, &N->sums_host, NDT_ROW * sizeof(double)) != hipSuccess ||
-      hipEventCreate(&N->ev_a) != hipSuccess || hipEventCreate(&N->ev_b) != hipSuccess) {
+  if (N->sums.create(ctx) != hipSuccess || hipEventCreate(&N->ev_a) != hipSuccess || hipEventCreate(&N->ev_b) != hipSuccess) {
     set_error(ctx, "allocation failed in pclhip_ndt_create");
     pclhip_ndt_destroy(N);
     return PCLHIP_ERR_HIP;
@@ -415,15 +386,13 @@ void pclhip_ndt_destroy(pclhip_ndt* N) {
   (void)hipStreamSynchronize(ctx->stream);
   ndt_drop_fitness(N, true);
   ndt_drop_cells(N);
-  ndt_free(ctx, N->tgt);
-  ndt_free(ctx, N->src);
-  ndt_free(ctx, N->src_sorted);
-  ndt_free(ctx, N->lists);
-  ndt_free(ctx, N->partials);
-  ndt_free(ctx, N->sums_dev);
+  dev_free_if(ctx, N->tgt);
+  dev_free_if(ctx, N->src);
+  dev_free_if(ctx, N->src_sorted);
+  dev_free_if(ctx, N->lists);
+  N->sums.release(ctx);
   if (N->ev_a) (void)hipEventDestroy(N->ev_a);
   if (N->ev_b) (void)hipEventDestroy(N->ev_b);
-  if (N->sums_host) pinned_free(ctx, N->sums_host, NDT_ROW * sizeof(double));
   delete N;
 }
 
@@ -451,12 +420,10 @@ pclhip_status pclhip_ndt_set_source(pclhip_ndt* N, const void* points, size_t st
   PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
   ndt_drop_fitness(N, false);
   N->src_n = 0;
-  ndt_free(ctx, N->src_sorted);
-  ndt_free(ctx, N->lists);
-  ndt_free(ctx, N->partials);
+  dev_free_if(ctx, N->src_sorted);
+  dev_free_if(ctx, N->lists);
   N->src_sorted = nullptr;
   N->lists = nullptr;
-  N->partials = nullptr;
   pclhip_status st = ndt_copy_records(ctx, points, stride, n, &N->src);
   if (st != PCLHIP_OK) return st;
   N->src_stride = stride;
@@ -476,9 +443,9 @@ pclhip_status pclhip_ndt_set_source(pclhip_ndt* N, const void* points, size_t st
   }
   const uint64_t want = (uint64_t(ngroups) + NDT_WAVES - 1) / NDT_WAVES;
   const uint64_t cap = uint64_t(per_cu) * uint64_t(ctx->num_cus > 0 ? ctx->num_cus : 1);
-  N->blocks = int(want < cap ? (want > 0 ? want : 1) : cap);
-  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &N->lists, size_t(N->blocks) * NDT_BLOCK * NDT_LIST_CAP * sizeof(uint32_t)));
-  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &N->partials, size_t(N->blocks) * NDT_ROW * sizeof(double)));
+  const int blocks = int(want < cap ? (want > 0 ? want : 1) : cap);
+  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &N->lists, size_t(blocks) * NDT_BLOCK * NDT_LIST_CAP * sizeof(uint32_t)));
+  PCLHIP_CHECK_HIP(ctx, N->sums.resize(ctx, blocks));
   N->src_n = n;
   return PCLHIP_OK;
 }
@@ -508,11 +475,11 @@ pclhip_status pclhip_ndt_align(pclhip_ndt* N, const pclhip_ndt_params* P, const 
     N->evals[v] = 0;
     N->eval_ms[v] = 0.0;
   }
-  const float* guess = guess_in ? guess_in : kNdtIdent;
+  const float* guess = guess_in ? guess_in : kIdentity16;
   NdtState S;
-  std::memcpy(S.final_T, kNdtIdent, sizeof S.final_T);  // Registration::align: final_transformation_ = Identity
+  std::memcpy(S.final_T, kIdentity16, sizeof S.final_T);  // Registration::align: final_transformation_ = Identity
   float Tk[16];
-  std::memcpy(Tk, kNdtIdent, sizeof Tk);
+  std::memcpy(Tk, kIdentity16, sizeof Tk);
   int nr = 0, ntrace = 0;
   bool converged = false;
   double score = 0.0;
@@ -521,7 +488,7 @@ pclhip_status pclhip_ndt_align(pclhip_ndt* N, const pclhip_ndt_params* P, const 
     double d1, d2;
     nf::gauss_constants(P->resolution, P->outlier_ratio, &d1, &d2);
     bool is_ident = true;
-    for (int k = 0; k < 16; ++k) is_ident = is_ident && guess[k] == kNdtIdent[k];
+    for (int k = 0; k < 16; ++k) is_ident = is_ident && guess[k] == kIdentity16[k];
     if (!is_ident) std::memcpy(S.final_T, guess, sizeof S.final_T);
     double x[6];
     nf::euler_from(S.final_T, x);

@@ -13,8 +13,8 @@
 //   sor_dist_heap_kernel   the same for K > 64 with a per-thread max-heap of floats in global memory (grid-sized, not
 //                          query-sized)
 //   ror_count_kernel       capped count of the points with d2 <= t: a lane stops wanting leaves once it has min_pts + 1
-//   sor_partial_kernel     per-entry distances in query order + per-block (sum, sq_sum, valid) in double, fixed order
-//   sor_finalize_kernel    the block sums in a fixed order (no atomics) -> mean, stddev, threshold on the device
+//   sor_partial_kernel     per-entry distances in query order + per-block (sum, sq_sum, valid) in double
+//   sor_finalize_kernel    the block sums -> mean, stddev, threshold on the device (both: the fixed order of block_sums.hpp)
 //   outlier_keep_kernel    classification; the keep flags are scanned (device_scan.hpp) and
 //   outlier_emit_kernel    writes the kept and removed ids, stable, in query order.
 #pragma once
@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <limits>
 
+#include "block_sums.hpp"
 #include "device_scan.hpp"
 #include "traverse.hpp"
 
@@ -285,76 +286,43 @@ __global__ __launch_bounds__(OR_BLOCK) void ror_count_kernel(IndexView ix, const
 }
 
 // per entry: the distance in query order (0 for a non-finite record) and per block (sum d, sum fl(d*d), valid) in double.
-// Thread t of block b sums entries b * OR_CHUNK + t * OR_PER + [0, OR_PER) in order, then the block's threads are summed
-// by a fixed butterfly and the four waves in order: the same sums for the same input, on every run.
+// Thread t of block b sums entries b * OR_CHUNK + t * OR_PER + [0, OR_PER) in order, then block_rows: the order depends
+// on the input alone, not on the device's grid.
 __global__ __launch_bounds__(OR_BLOCK) void sor_partial_kernel(const uint32_t* __restrict__ epos, uint32_t m,
                                                              const float* __restrict__ dpos, float* __restrict__ dist,
                                                              double* __restrict__ partial) {
   const uint64_t base = uint64_t(blockIdx.x) * OR_CHUNK + uint64_t(threadIdx.x) * OR_PER;
-  double s = 0.0, ss = 0.0, v = 0.0;
+  double acc[3] = {0.0, 0.0, 0.0};  // sum, sq_sum, valid
   for (int e = 0; e < OR_PER; ++e) {
     const uint64_t j = base + e;
     if (j < m) {
       const uint32_t pos = epos[j];
       const float d = pos != NO_INDEX ? dpos[pos] : 0.0f;
       dist[j] = d;
-      s += double(d);
-      ss += double(__fmul_rn(d, d));
-      v += pos != NO_INDEX ? 1.0 : 0.0;
+      acc[0] += double(d);
+      acc[1] += double(__fmul_rn(d, d));
+      acc[2] += pos != NO_INDEX ? 1.0 : 0.0;
     }
   }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
-  v = wave_sum_d(v);
-  __shared__ double ws[OR_WAVES][3];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  if (lane == 0) {
-    ws[wave][0] = s;
-    ws[wave][1] = ss;
-    ws[wave][2] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int w = 0; w < OR_WAVES; ++w) {
-      a += ws[w][0];
-      b += ws[w][1];
-      c += ws[w][2];
-    }
-    partial[3 * blockIdx.x] = a;
-    partial[3 * blockIdx.x + 1] = b;
-    partial[3 * blockIdx.x + 2] = c;
-  }
+  block_rows<3, OR_WAVES, 3>(acc, partial);
 }
 
-// one block: the block sums in a fixed order -> stats[0..5] = mean, stddev, threshold, sum, sq_sum, valid
+// one block: thread t adds the rows t, t + OR_BLOCK, ..., then the wave and block steps -> stats[0..5] = mean, stddev,
+// threshold, sum, sq_sum, valid
 // (statistical_outlier_removal.hpp:104-117: mean = sum / valid, variance = (sq_sum - sum^2 / valid) / (valid - 1))
 __global__ __launch_bounds__(OR_BLOCK) void sor_finalize_kernel(const double* __restrict__ partial, uint32_t nb,
                                                               double std_mul, double* __restrict__ stats) {
-  double s = 0.0, ss = 0.0, v = 0.0;
+  double acc[3] = {0.0, 0.0, 0.0};
   for (uint32_t b = threadIdx.x; b < nb; b += OR_BLOCK) {
-    s += partial[3 * b];
-    ss += partial[3 * b + 1];
-    v += partial[3 * b + 2];
+    acc[0] += partial[3 * b];
+    acc[1] += partial[3 * b + 1];
+    acc[2] += partial[3 * b + 2];
   }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
-  v = wave_sum_d(v);
   __shared__ double ws[OR_WAVES][3];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  if (lane == 0) {
-    ws[wave][0] = s;
-    ws[wave][1] = ss;
-    ws[wave][2] = v;
-  }
+  wave_rows(acc, ws);
   __syncthreads();
   if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int w = 0; w < OR_WAVES; ++w) {
-      a += ws[w][0];
-      b += ws[w][1];
-      c += ws[w][2];
-    }
+    const double a = block_column<OR_WAVES>(ws, 0), b = block_column<OR_WAVES>(ws, 1), c = block_column<OR_WAVES>(ws, 2);
     const double mean = a / c;
     const double var = (b - a * a / c) / (c - 1.0);
     const double sd = sqrt(var);

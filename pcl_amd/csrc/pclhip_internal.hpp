@@ -366,6 +366,10 @@ inline hipError_t pinned_malloc(pclhip_ctx* ctx, T** p, size_t bytes) {
   return pinned_malloc(ctx, reinterpret_cast<void**>(p), bytes);
 }
 void dev_free(pclhip_ctx* ctx, void* p);
+inline void dev_free_if(pclhip_ctx* ctx, void* p) {
+  if (p) dev_free(ctx, p);
+}
+constexpr float kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 void dev_cache_release(pclhip_ctx* ctx);  // really frees every cached block
 pclhip_status reserve_arena(pclhip_ctx* ctx, size_t bytes);
 // reserve the context's arena for clouds of `points` points (no-op when one exists or PCLHIP_ARENA_MB=0)
@@ -396,8 +400,7 @@ struct DeviceScope {
   DeviceScope() = default;
   explicit DeviceScope(pclhip_ctx* c) : ctx(c) {}
   ~DeviceScope() {
-    for (void* p : mem)
-      if (p) dev_free(ctx, p);
+    for (void* p : mem) dev_free_if(ctx, p);
     for (hipEvent_t e : events)
       if (e) (void)hipEventDestroy(e);
   }

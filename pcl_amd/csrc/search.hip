@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "traverse.hpp"
+#include "block_sums.hpp"
 #include "standoff.hpp"
 #include "normals_math.hpp"
 #include "device_scan.hpp"
@@ -1698,13 +1699,7 @@ struct PairAcc {
       red_s[wave][28] = s1;
       red_s[wave][29] = s2;
     }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-      double s = 0.0;
-#pragma unroll
-      for (int w = 0; w < WAVES_PER_BLOCK; ++w) s += red_s[w][threadIdx.x];
-      partials[size_t(blockIdx.x) * NS + threadIdx.x] = s;
-    }
+    block_store<NS, WAVES_PER_BLOCK, NS>(red_s, partials);  // (block_sums.hpp)
   }
 };
 
@@ -2247,33 +2242,19 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
 
 // ---- Registration::getFitnessScore (registration/include/pcl/registration/impl/registration.hpp:132-168)
 // Mean of the 1-NN squared distances that are <= max_range (the reference compares the SQUARED distance
-// with max_range as given, in double).  Per-block partial (sum, count) pairs, summed on the host in
+// with max_range as given, in double).  Per-block partial (sum, count) pairs (block_sums.hpp), summed on the host in
 // block order: deterministic.
 __global__ __launch_bounds__(BLOCK) void fitness_partial_kernel(const float* __restrict__ d2, uint32_t n,
                                                                 double max_range, double* __restrict__ partials) {
-  __shared__ double red_s[WAVES_PER_BLOCK][2];
-  double s = 0.0, c = 0.0;
+  double acc[2] = {0.0, 0.0};  // sum, count
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float d = d2[i];
     if (double(d) <= max_range) {  // +inf (no match / non-finite source point) never passes
-      s += double(d);
-      c += 1.0;
+      acc[0] += double(d);
+      acc[1] += 1.0;
     }
   }
-  s = wave_sum_d(s);
-  c = wave_sum_d(c);
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  if (lane == 0) {
-    red_s[wave][0] = s;
-    red_s[wave][1] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double a = 0.0;
-#pragma unroll
-    for (int w = 0; w < WAVES_PER_BLOCK; ++w) a += red_s[w][threadIdx.x];
-    partials[size_t(blockIdx.x) * 2 + threadIdx.x] = a;
-  }
+  block_rows<2, WAVES_PER_BLOCK, 2>(acc, partials);
 }
 
 pclhip_status launch_fitness_score(pclhip_icp* icp, const float T[16], double max_range, double* score,
@@ -2286,8 +2267,7 @@ pclhip_status launch_fitness_score(pclhip_icp* icp, const float T[16], double ma
   double sum = 0.0, cnt = 0.0;
   if (icp->n > 0) {
   const IndexView v = icp->target->view();
-  Mat34 M;
-  for (int i = 0; i < 12; ++i) M.m[i] = T[i];
+  const Mat34 M = mat34_of(T);
   const uint32_t n = icp->n;
   const int gr = ctx->num_cus * 4;
   // scratch: transformed copy of the source, seed/match positions, match ids, distances, partials

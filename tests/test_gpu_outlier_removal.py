@@ -168,6 +168,68 @@ def test_sor_mean_k_buckets(gpu, bunny, mean_k):
     check_sor(f, kept, rs.statistical_outlier_removal(b, mean_k, 1.0), "mean_k=%d" % mean_k)
 
 
+def _butterfly_then_waves(x):
+    """x[..., 256]: per column the 64-lane xor butterfly (every lane adds its partner's value, offsets 32 .. 1; lane 0
+    is read), then the four waves in order from 0.0"""
+    x = x.reshape(x.shape[:-1] + (4, 64))
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        x = x + x[..., lane ^ o]
+    a = np.zeros(x.shape[:-2], np.float64)
+    for w in range(4):
+        a = a + x[..., w, 0]
+    return a
+
+
+def sor_sums_in_kernel_order(d, valid):
+    """(sum, sq_sum, valid) of the float32 distances d as sor_partial_kernel / sor_finalize_kernel add them
+    (pcl_amd/csrc/block_sums.hpp; OR_BLOCK 256 threads, OR_PER 16 entries per thread, OR_CHUNK 4096 entries per block)."""
+    m = len(d)
+    nb = (m + 4095) // 4096
+    cols = np.zeros((3, nb * 4096), np.float64)  # (entries past m are skipped by the kernel; x + 0.0 has the bits of x here:
+    cols[0, :m] = d                              # no sum is -0.0)
+    cols[1, :m] = d * d                          # the square in float, then widened
+    cols[2, :m] = valid
+    cols = cols.reshape(3, nb, 256, 16)
+    acc = np.zeros((3, nb, 256), np.float64)
+    for e in range(16):  # a thread's 16 entries in order
+        acc = acc + cols[..., e]
+    rows = _butterfly_then_waves(acc)  # [3, nb]: one row per block
+    acc = np.zeros((3, 256), np.float64)
+    for b in range(0, nb, 256):  # finalize: thread t adds the rows t, t + 256, ...
+        part = rows[:, b:b + 256]
+        acc[:, :part.shape[1]] = acc[:, :part.shape[1]] + part
+    return _butterfly_then_waves(acc)
+
+
+# the smallest sizes at which a level of the order can go wrong: several blocks and a ragged last thread (4 rows: the
+# finalize stride does not wrap); 259 rows: the finalize stride wraps for the first three threads, the last row has one entry
+@pytest.mark.parametrize("m", [3 * 4096 + 5, 257 * 4096 + 4097], ids=["blocks", "stride_wraps"])
+def test_sor_sums_have_the_documented_order(gpu, m):
+    """sum, sq_sum and valid are not just repeatable: they are the sums in the order block_sums.hpp documents, restated
+    here from the returned distances, bit for bit -- and mean, stddev, threshold follow from them by the kernel's three
+    expressions."""
+    from pcl_amd import synth
+    c = synth.gaussian_surface(m)[:, :3].copy()
+    nan_rows = np.random.default_rng(5).choice(m, 37, replace=False)
+    c[nan_rows, 1] = np.nan
+    std_mul = 1.5
+    f, _ = sor(gpu, c, 4, std_mul)
+    d = np.asarray(f.lastMeanDistances())
+    valid = np.isfinite(c).all(1)
+    assert d.dtype == np.float32 and len(d) == m and not d[~valid].any() and np.isfinite(d).all()
+    a, b, n = sor_sums_in_kernel_order(d, valid)
+    assert n == m - 37
+    mean = a / n
+    sd = np.sqrt((b - a * a / n) / (n - 1.0))
+    ref = dict(sum=a, sq_sum=b, valid=n, mean=mean, stddev=sd, threshold=mean + np.float64(std_mul) * sd)
+    st = f.lastStatistics()
+    for k, r in ref.items():
+        got = np.float64(st[k])
+        print("%s: device %r restated %r" % (k, float(got), float(r)))
+        assert got.view(np.uint64) == np.float64(r).view(np.uint64), (k, float(got), float(r))
+
+
 def test_edges(gpu):
     import pcl_amd
     nan = np.float32("nan")
