@@ -267,6 +267,32 @@ PCLHIP_API pclhip_status pclhip_radius_outlier_removal(pclhip_index* index, cons
                                                        double radius, int min_pts, int is_dense, int negative,
                                                        int32_t* kept, uint64_t* n_kept, int32_t* removed,
                                                        uint64_t* n_removed);
+/* pcl::FPFHEstimation<PointInT, PointNT, PointOutT>::computeFeature with setRadiusSearch (features/include/pcl/features/
+ * impl/fpfh.hpp:51-303, pcl::computePairFeatures of features/src/pfh.cpp:45-103): search surface == input, 11 / 11 / 11
+ * bins.  `index` is built over the whole unscaled cloud and holds normals (pclhip_normals* or pclhip_index_set_normals):
+ * PCLHIP_ERR_STATE without them; radius <= 0 is PCLHIP_ERR_INVALID.  The neighbourhood is every indexed point with float
+ * d2 < float(radius * radius), the point itself included (as pclhip_radius_search).
+ *   out       (host or device) 33 floats (f1, f2, f3 histograms) at byte 0 of each out_stride_bytes record, one per query:
+ *             every record of the cloud, or indices[0..n_indices) in that order
+ *   out_spfh  (host or device, optional) the 33-float SPFH rows (computePointSPFHSignature), dense, one per ORIGINAL
+ *             record
+ * The SPFH values are the reference's bit for bit wherever its float pair features and this device's fall into the same
+ * bins (hist_incr added once per hit, in float: independent of the neighbours' order).  The weighting sums the exact
+ * double products of SPFH value and float weight 1.0f / d2 in double, in traversal order, where the reference sums float
+ * products in float in ascending distance; each histogram is then scaled by 100.0 / sum in double as the reference does.
+ * A point with no neighbour but itself gets an all-zero row.  A record the index dropped (non-finite) gets 33 NaN in
+ * both outputs and is counted in out_nan_count.
+ * Deviation -- non-finite normals (the reference casts a NaN feature to int: undefined): a point whose own normal is not
+ * finite gets 33 NaN in both outputs and is counted; a neighbour whose normal is not finite is skipped in both passes
+ * but still counts towards hist_incr = 100 / (neighbours - 1).
+ * Cost with `indices`: the SPFH pass still runs over the WHOLE cloud (the reference computes only the union of the
+ * queries' neighbourhoods); only the weighting pass is restricted to the queries.
+ * A neighbourhood of more than 65536 points is PCLHIP_ERR_OVERFLOW (a bin counter holds 16 bits; nothing is truncated).
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_fpfh_ms that of its two passes. */
+PCLHIP_API pclhip_status pclhip_fpfh(pclhip_index* index, const int32_t* indices, uint64_t n_indices, double radius,
+                                     void* out, size_t out_stride_bytes, float* out_spfh, uint64_t* out_nan_count);
+/* GPU time (ms) of the SPFH kernel and of the weighting kernel of the last pclhip_fpfh on this index. */
+PCLHIP_API void pclhip_index_last_fpfh_ms(const pclhip_index* index, double* spfh_ms, double* weight_ms);
 /* GPU time (ms) of the last pclhip_knn / pclhip_normals traversal kernel on this index. */
 PCLHIP_API double pclhip_index_last_kernel_ms(const pclhip_index* index);
 /* Supply target normals computed elsewhere (e.g. a pcl::PointNormal target: normals = points + 16,

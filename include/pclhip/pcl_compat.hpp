@@ -545,6 +545,92 @@ class NormalEstimationOMP : public NormalEstimation<PointInT> {
   unsigned int threads_ = 0;
 };
 
+// pcl::FPFHSignature33 (common/include/pcl/impl/point_types.hpp): 33 floats, f1 | f2 | f3 histograms
+struct FPFHSignature33 {
+  float histogram[33] = {0};
+  static constexpr int descriptorSize() { return 33; }
+};
+static_assert(sizeof(FPFHSignature33) == 132, "pcl::FPFHSignature33 record size");
+
+// pcl::FPFHEstimation<PointInT, PointNT, PointOutT> (features/include/pcl/features/fpfh.h:79-222, impl/fpfh.hpp:51-303)
+// with setRadiusSearch over pclhip_fpfh: the search surface is the input cloud, 11 / 11 / 11 subdivisions.  compute()
+// leaves the output empty for what this path does not build (setKSearch, another search surface, other subdivisions, a
+// foreign Search object).  PointNT is pcl::Normal or pcl::PointNormal.
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33>
+class FPFHEstimation : public PCLBase<PointInT> {
+  static_assert(sizeof(PointOutT) == 132, "the output type is pcl::FPFHSignature33");
+ public:
+  using SearchPtr = typename search::Search<PointInT>::Ptr;
+  using PointCloudOut = PointCloud<PointOutT>;
+  using PointCloudNConstPtr = typename PointCloud<PointNT>::ConstPtr;
+  FPFHEstimation() : FPFHEstimation(Context::defaultContext()) {}
+  explicit FPFHEstimation(Context::Ptr ctx) : ctx_(std::move(ctx)) {}
+  void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }  // feature.h:339-349
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setSearchMethod(const SearchPtr& tree) { tree_ = tree; }
+  SearchPtr getSearchMethod() const { return tree_; }
+  void setSearchSurface(const typename PointCloud<PointInT>::ConstPtr& cloud) { surface_ = cloud; }
+  typename PointCloud<PointInT>::ConstPtr getSearchSurface() const { return surface_; }
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double radius) { radius_ = radius; }
+  double getRadiusSearch() const { return radius_; }
+  double getSearchParameter() const { return k_ >= 1 ? double(k_) : radius_; }
+  void setNrSubdivisions(int nr_bins_f1, int nr_bins_f2, int nr_bins_f3) { bins_[0] = nr_bins_f1; bins_[1] = nr_bins_f2; bins_[2] = nr_bins_f3; }
+  void getNrSubdivisions(int& nr_bins_f1, int& nr_bins_f2, int& nr_bins_f3) const { nr_bins_f1 = bins_[0]; nr_bins_f2 = bins_[1]; nr_bins_f3 = bins_[2]; }
+  std::uint64_t getNaNCount() const { return nan_; }
+  void compute(PointCloudOut& output) {
+    output.points.clear();
+    output.is_dense = true;
+    const auto& input = this->input_;
+    if (!input || !normals_ || normals_->size() != input->size()) return;  // feature.hpp:241-250
+    if (k_ != 0 || !(radius_ > 0.0) || (surface_ && surface_ != input)) return;
+    if (bins_[0] != 11 || bins_[1] != 11 || bins_[2] != 11) return;
+    if (!tree_) tree_ = std::make_shared<search::KdTree<PointInT>>(ctx_);
+    auto* dev = dynamic_cast<search::KdTree<PointInT>*>(tree_.get());
+    if (dev == nullptr) return;
+    if (dev->getInputCloud() != input || dev->handle() == nullptr) {
+      if (!dev->setInputCloud(input)) return;
+    }
+    if (input->size() > 0 &&
+        pclhip_index_set_normals(dev->handle(), &normals_->points[0].normal_x, sizeof(PointNT)) != PCLHIP_OK)
+      return;
+    const bool subset = this->indices_ && !this->fake_indices_;
+    const std::size_t m = subset ? this->indices_->size() : input->size();
+    output.resize(m);
+    nan_ = 0;
+    if (pclhip_fpfh(dev->handle(), subset ? this->indices_->data() : nullptr, subset ? m : 0, radius_, output.points.data(),
+                    sizeof(PointOutT), nullptr, &nan_) != PCLHIP_OK) {
+      output.points.clear();
+      return;
+    }
+    output.is_dense = (nan_ == 0);  // fpfh.hpp:248-261
+  }
+ private:
+  Context::Ptr ctx_;
+  SearchPtr tree_;
+  typename PointCloud<PointInT>::ConstPtr surface_;
+  PointCloudNConstPtr normals_;
+  int k_ = 0;
+  double radius_ = 0.0;
+  int bins_[3] = {11, 11, 11};
+  std::uint64_t nan_ = 0;
+};
+
+// pcl::FPFHEstimationOMP (features/include/pcl/features/fpfh_omp.h): the same computation; the thread count is only stored
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33>
+class FPFHEstimationOMP : public FPFHEstimation<PointInT, PointNT, PointOutT> {
+ public:
+  explicit FPFHEstimationOMP(unsigned int nr_threads = 0) : FPFHEstimation<PointInT, PointNT, PointOutT>() { setNumberOfThreads(nr_threads); }
+  explicit FPFHEstimationOMP(Context::Ptr ctx, unsigned int nr_threads = 0) : FPFHEstimation<PointInT, PointNT, PointOutT>(std::move(ctx)) {
+    setNumberOfThreads(nr_threads);
+  }
+  void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }
+  unsigned int getNumberOfThreads() const { return threads_; }
+ private:
+  unsigned int threads_ = 0;
+};
+
 namespace registration {
 
 // pcl::registration::CorrespondenceRejector{Distance,MedianDistance,OneToOne,Trimmed}: parameter holders;

@@ -5,6 +5,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::registration::CorrespondenceEstimation          registration/include/pcl/registration/correspondence_estimation.h
   pcl::IterativeClosestPoint / ...WithNormals          registration/include/pcl/registration/icp.h:98-347,360-440
   pcl::NormalEstimation                                features/include/pcl/features/normal_3d.h:243-420
+  pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
 Clouds are (n, c>=3) float32 arrays: numpy (host) or torch CUDA tensors (device-resident; only the
 pointer crosses the boundary).  All compute happens in libpclhip.so; there is no CPU fallback.
@@ -1955,3 +1956,106 @@ class RadiusOutlierRemoval(_OutlierRemoval):
     def _call(self, h, iptr, m, kp, nk, rp, nr):
         return self.lib.pclhip_radius_outlier_removal(h, iptr, m, self._radius, self._min_pts, int(self._dense()),
                                                       int(self._negative), kp, nk, rp, nr)
+
+
+class FPFHEstimation:
+    """pcl::FPFHEstimation<PointInT, PointNT, pcl::FPFHSignature33> with setRadiusSearch (features/include/pcl/features/
+    fpfh.h, impl/fpfh.hpp:51-303) over pclhip_fpfh: search surface == input, 11 / 11 / 11 bins.  The normals are the ones
+    given with setInputNormals, or the ones the tree already holds (a NormalEstimation that ran on the same tree)."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.tree = None
+        self.radius = 0.0
+        self.cloud = None
+        self.normals = None
+        self.indices = None
+        self.nan_count = 0
+
+    def setInputCloud(self, cloud):
+        self.cloud = cloud
+
+    def setInputNormals(self, normals):
+        """FeatureFromNormals::setInputNormals (feature.h:339-349): one normal per record of the input cloud, (n, c >= 3)."""
+        self.normals = normals
+
+    def getInputNormals(self):
+        return self.normals
+
+    def setSearchMethod(self, tree):
+        self.tree = tree
+
+    def getSearchMethod(self):
+        return self.tree
+
+    def setIndices(self, indices):
+        """PCLBase::setIndices: one descriptor per input[indices[j]], in that order (None: every record)."""
+        self.indices = None if indices is None else np.ascontiguousarray(indices, np.int32)
+
+    def setRadiusSearch(self, radius):
+        self.radius = float(radius)
+
+    def getRadiusSearch(self):
+        return self.radius
+
+    def setKSearch(self, k):
+        if int(k) != 0:
+            raise NotImplementedError("FPFHEstimation searches by radius only (setRadiusSearch)")
+
+    def getKSearch(self):
+        return 0
+
+    def lastPassMs(self):
+        """GPU time (ms) of the SPFH kernel and of the weighting kernel of the last compute()."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self.lib.pclhip_index_last_fpfh_ms(self.tree.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def _run(self, want_fpfh, want_spfh):
+        if self.radius == 0.0:  # Feature::initCompute (impl/feature.hpp:131-155)
+            raise ValueError("Neither radius nor K defined! Set one of them to a positive number first")
+        if self.tree is None:
+            self.tree = KdTree(self.ctx)
+        if self.tree.h is None or self.tree._cloud_id != (id(self.cloud), None):
+            self.tree.setInputCloud(self.cloud)
+        if self.normals is not None:
+            self.tree.setNormals(self.normals)
+        n = self.tree.n_cloud
+        m = n if self.indices is None else len(self.indices)
+        torch_out = _is_torch(self.cloud)
+        if torch_out:
+            import torch
+
+            def make(rows):
+                t = torch.empty((rows, 33), dtype=torch.float32, device=self.cloud.device)
+                return t, C.c_void_p(t.data_ptr())
+        else:
+            def make(rows):
+                a = np.empty((rows, 33), np.float32)
+                return a, C.c_void_p(a.ctypes.data)
+        out, optr = make(m if want_fpfh else 0)
+        spfh, sptr = make(n) if want_spfh else (None, None)
+        nan = C.c_uint64(0)
+        none = np.zeros(1, np.int32)
+        if want_fpfh:
+            ind = None if self.indices is None else C.c_void_p(self.indices.ctypes.data)
+            ni = 0 if self.indices is None else m
+        else:  # an empty index list: no query, the SPFH pass alone
+            ind, ni = C.c_void_p(none.ctypes.data), 0
+        check(self.lib.pclhip_fpfh(self.tree.h, ind, ni, self.radius, optr, 132, C.cast(sptr, C.POINTER(C.c_float)),
+                                   C.byref(nan)), self.ctx.h)
+        self.nan_count = int(nan.value)
+        return out, spfh
+
+    def compute(self):
+        """-> (m, 33) float32: the f1, f2 and f3 histograms of every query (NaN rows are counted in nan_count)."""
+        return self._run(True, False)[0]
+
+    def computeSPFH(self):
+        """-> (n, 33) float32: the SPFH signature of every record of the input cloud (computePointSPFHSignature)."""
+        return self._run(False, True)[1]
+
+    def computeBoth(self):
+        """-> ((m, 33) FPFH, (n, 33) SPFH) of one call."""
+        return self._run(True, True)

@@ -1361,6 +1361,31 @@ pclhip_status pclhip_radius_outlier_removal(pclhip_index* ix, const int32_t* ind
   return outlier_filter(ix, indices, n_indices, prm, kept, n_kept, removed, n_removed, nullptr, nullptr);
 }
 
+// ---- FPFHEstimation (fpfh.hpp) -------------------------------------------------------------------
+pclhip_status pclhip_fpfh(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius, void* out,
+                          size_t out_stride, float* out_spfh, uint64_t* out_nan_count) {
+  if (!ix) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  if (out_nan_count) *out_nan_count = 0;
+  PCLHIP_REQUIRE(ctx, radius > 0.0, "radius must be > 0");
+  PCLHIP_REQUIRE(ctx, !ix->scaled, "FPFH needs an index built in the cloud's own coordinates (no rescaling representation)");
+  PCLHIP_REQUIRE(ctx, indices != nullptr || n_indices == 0, "null indices");
+  const uint64_t m = indices ? n_indices : ix->n_orig;
+  PCLHIP_REQUIRE(ctx, out != nullptr || m == 0, "null buffer");
+  PCLHIP_REQUIRE(ctx, m == 0 || (out_stride >= 132 && out_stride % 4 == 0), "stride must be a multiple of 4 and >= 132 bytes");
+  if (!ix->has_normals) {
+    set_error(ctx, "FPFH needs normals in the index: pclhip_normals* or pclhip_index_set_normals first");
+    return PCLHIP_ERR_STATE;
+  }
+  return fpfh_compute(ix, indices, n_indices, radius, out, out_stride, out_spfh, out_nan_count);
+}
+
+void pclhip_index_last_fpfh_ms(const pclhip_index* ix, double* spfh_ms, double* weight_ms) {
+  if (spfh_ms) *spfh_ms = ix ? ix->fpfh_pass_ms[0] : 0.0;
+  if (weight_ms) *weight_ms = ix ? ix->fpfh_pass_ms[1] : 0.0;
+}
+
 // ------------------------------------------------------------------------------------------------
 void pclhip_icp_params_default(pclhip_icp_params* p) {
   if (!p) return;

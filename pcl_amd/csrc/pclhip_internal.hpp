@@ -266,6 +266,7 @@ struct pclhip_index {
   float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
   double build_ms = 0;
   double last_kernel_ms = 0;
+  double fpfh_pass_ms[2] = {0, 0};  // the SPFH and the weighting kernel of the last pclhip_fpfh
   bool has_normals = false;
   bool scaled = false;              // built through a rescaling point representation: coordinates * scale
   float scale[3] = {1, 1, 1};
@@ -526,6 +527,10 @@ struct OutlierParams {
 pclhip_status outlier_filter(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, const OutlierParams& prm,
                              int32_t* kept, uint64_t* n_kept, int32_t* removed, uint64_t* n_removed, float* mean_dist,
                              double* stats6);
+// FPFHEstimation over the index (fpfh.hpp, compiled into radius.hip): 33 floats per query at out + j * out_stride, the SPFH
+// rows per original record to out_spfh (optional)
+pclhip_status fpfh_compute(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius, void* out,
+                           size_t out_stride, float* out_spfh, uint64_t* out_nan_count);
 // NormalDistributionsTransform: the voxel Gaussians of a target cloud (ndt_cells.hpp, compiled into voxelgrid.hip), in
 // ascending voxel id.  Device arrays owned by the struct (ndt_free_cells).
 struct NdtCells {

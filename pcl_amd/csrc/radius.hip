@@ -430,3 +430,6 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 
 // NormalDistributionsTransform: its derivative pass is a radius traversal of the index over the voxel centroids
 #include "ndt.hpp"
+
+// FPFHEstimation: two radius traversals of the index with per-point histograms
+#include "fpfh.hpp"
