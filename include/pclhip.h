@@ -749,6 +749,107 @@ PCLHIP_API pclhip_status pclhip_ndt_cells(pclhip_ndt* ndt, const pclhip_ndt_para
 PCLHIP_API pclhip_status pclhip_ndt_fitness_score(pclhip_ndt* ndt, const float T[16], double max_range, double* score,
                                                  uint64_t* nr);
 
+/* ---- SampleConsensusPrerejective ------------------------------------------------------------------
+ * Replaces pcl::SampleConsensusPrerejective<PointXYZ, PointXYZ, FeatureT> (registration/include/pcl/registration/
+ * sample_consensus_prerejective.h, impl/sample_consensus_prerejective.hpp:78-348) with its polygonal pre-rejection
+ * (correspondence_rejection_poly.h:208-338) and TransformationEstimationSVD.  Bound to a target index built over the
+ * whole unscaled target cloud.  Per iteration: selectSamples (:96-117), one of the k nearest target features of each
+ * sample (:123-153), thresholdPolygon, umeyama on the pairs (double, demeaned), getFitness (:310-348), acceptance
+ * (:284-293): float(inliers) / float(source size) >= inlier_fraction && error < lowest error -- strict, the earliest
+ * iteration wins a tie; a guess that is not isApprox(Identity, 0.01f) is scored first (:233-243).
+ * Deviations:
+ *   - random numbers: a draw is a pure function of (seed, iteration, slot) -- splitmix64's finalizer over
+ *     seed + 0x9E3779B97F4A7C15 * ((iteration << 8 | slot) + 1), u = (x >> 11) * 2^-53, index = int(n * u), which mirrors
+ *     n * (rand() / (RAND_MAX + 1.0)).  Slots 0 .. nr_samples-1 are the sample draws, nr_samples .. 2 nr_samples-1 the
+ *     picks among the k neighbours.  The reference's rand() sequence cannot be reproduced across libcs; with this one the
+ *     result does not depend on how iterations are batched (batch_size changes nothing) and a test can replay the draws.
+ *     The reference's feature-neighbour cache is an optimisation, not a semantic: it is kept as one (a source row is
+ *     searched once per source / target feature set).
+ *   - the error is float(sum / count) with the float d2 values summed in double in a fixed order (per 64-point group of
+ *     the source's kd order a wave tree, then the groups in the order of block_sums_finalize_kernel), where the reference
+ *     adds floats sequentially: they differ by at most (count + 4) * 2^-24 relative.  Two runs give the same bits.
+ *   - nr_samples <= 8 (the trace record and the per-thread state hold that many); k_correspondences <= 32.
+ *   - k is clamped to the number of finite target feature rows (the pick is drawn among that many); a sampled source row
+ *     that is not finite has no neighbour and its hypothesis counts as rejected (the reference asserts inside FLANN); so
+ *     does one whose chosen target record is not finite.
+ * Not built: SampleConsensusInitialAlignment, a user-supplied transformation estimator, setIndices, multi-GPU, early
+ * abandonment of a hypothesis that can no longer win, CorrespondenceRejectorPoly as a rejector of the ICP chain. */
+typedef struct pclhip_scp pclhip_scp;
+typedef struct {
+  int max_iterations;                  /* sample_consensus_prerejective.h:128, default 5000 */
+  int nr_samples;                      /* nr_samples_, default 3 (1 .. 8 here) */
+  int k_correspondences;               /* k_correspondences_ ("correspondence randomness"), default 2 (<= 32 here) */
+  float similarity_threshold;          /* :127, default 0.6f, in [0, 1[ */
+  float inlier_fraction;               /* inlier_fraction_, default 0, in [0, 1] */
+  double max_correspondence_distance;  /* registration.h corr_dist_threshold_, default sqrt(DBL_MAX) */
+  uint64_t seed;                       /* of the draws (above), default 0 */
+  int batch_size;                      /* iterations per batch of launches, default 2048; never changes a result */
+} pclhip_scp_params;
+typedef struct {
+  float final_transformation[16];   /* row-major; the guess when nothing was accepted */
+  int converged;
+  int iterations;                   /* max_iterations */
+  int rejected;                     /* iterations that did not reach getFitness (num_rejections) */
+  int best_iteration;               /* the accepted iteration; -1: the guess; -2: none */
+  float best_error;                 /* lowest_error (FLT_MAX when nothing was accepted) */
+  uint32_t best_count;              /* inliers of the accepted hypothesis */
+  int trace_count;                  /* entries written to the trace buffer */
+  uint32_t knn_rows;                /* source feature rows searched by this call */
+  double knn_ms, hypothesis_ms, fitness_ms;  /* GPU time of the launches by kind (HIP events) */
+  double total_ms;                  /* wall time of the call */
+} pclhip_scp_result;
+typedef struct {                    /* one entry per iteration (pclhip_scp_set_trace) */
+  int iteration;
+  int rejected;                     /* 0: scored; 1: thresholdPolygon; 2: a sample without a usable match */
+  int samples[8];                   /* selectSamples, ascending */
+  int matches[8];                   /* the chosen target indices (-1: none) */
+  float transformation[16];         /* the hypothesis (not rejected only) */
+  uint32_t inliers;                 /* getFitness of it */
+  float error;
+} pclhip_scp_trace;
+/* KdTreeFLANN<FeatureT>::nearestKSearch, exact, by brute force: the k target rows nearest to every query row under
+ * FLANN's L2_Simple<float> -- in float, dimension 0 .. D-1 in order, acc = acc + diff * diff, no contraction -- in
+ * ascending (d2, target index): ties go to the lower index.  Rows are D floats at the start of strided records, host or
+ * device; D <= 64, 1 <= k <= 32.  A target row that holds a non-finite value is never a candidate (convertCloudToArray
+ * drops it); counts[q] = min(k, finite target rows), PCLHIP_ERR_STATE when there is none; a query row that is not
+ * finite gets count 0.  out_indices / out_d2: k entries per query (-1 / +inf behind the count). */
+PCLHIP_API pclhip_status pclhip_feature_knn(pclhip_ctx* ctx, const void* target_rows, size_t target_stride_bytes,
+                                            uint64_t n_target, const void* query_rows, size_t query_stride_bytes,
+                                            uint64_t n_query, int D, int k, int32_t* out_indices, float* out_d2,
+                                            uint32_t* out_counts);
+PCLHIP_API void pclhip_scp_params_default(pclhip_scp_params* p);
+PCLHIP_API pclhip_status pclhip_scp_create(pclhip_index* target, pclhip_scp** out);
+PCLHIP_API void pclhip_scp_destroy(pclhip_scp* scp);
+/* setInputSource: strided records (x y z first), host or device; the registration keeps its own copy. */
+PCLHIP_API pclhip_status pclhip_scp_set_source(pclhip_scp* scp, const void* points, size_t stride_bytes, uint64_t n);
+/* setSourceFeatures / setTargetFeatures (:140-160): D floats at the start of each record, one per record of the cloud,
+ * in the cloud's order; copied. */
+PCLHIP_API pclhip_status pclhip_scp_set_source_features(pclhip_scp* scp, const void* rows, size_t stride_bytes, uint64_t n,
+                                                        int D);
+PCLHIP_API pclhip_status pclhip_scp_set_target_features(pclhip_scp* scp, const void* rows, size_t stride_bytes, uint64_t n,
+                                                        int D);
+/* Optional per-iteration record of the next alignments (NULL / 0: none); the buffer must outlive them.  With a trace the
+ * records of every batch are read back (one more synchronisation per batch). */
+PCLHIP_API pclhip_status pclhip_scp_set_trace(pclhip_scp* scp, pclhip_scp_trace* buf, int capacity);
+/* getFitness (:310-348) of n_transforms row-major 4x4 matrices (host) in batched launches: the source moved by T
+ * (Transformer::se3 order, as pclhip_transform_cloud order 1), the 1-NN in the target per point, inlier when float
+ * d2 < float(corr_dist * corr_dist); counts[h] inliers, errors[h] = float(sum / count) or FLT_MAX (exposed for tests). */
+PCLHIP_API pclhip_status pclhip_scp_evaluate(pclhip_scp* scp, const pclhip_scp_params* params, const float* transforms,
+                                            int n_transforms, uint32_t* counts, float* errors);
+/* Registration::align -> computeTransformation (:157-306).  guess: row-major 4x4 or NULL.  PCLHIP_ERR_STATE: features
+ * missing or not one per point (:161-190); PCLHIP_ERR_INVALID: inlier fraction outside [0, 1], similarity outside [0, 1[,
+ * k <= 0 (:192-212), nr_samples greater than the source size (:83-90). */
+PCLHIP_API pclhip_status pclhip_scp_align(pclhip_scp* scp, const pclhip_scp_params* params, const float guess[16],
+                                         pclhip_scp_result* result);
+/* getInliers (:240): the accepted hypothesis' inlier indices into the source, ascending; *count always, the indices when
+ * capacity >= *count (PCLHIP_ERR_OVERFLOW otherwise).  out: host. */
+PCLHIP_API pclhip_status pclhip_scp_inliers(pclhip_scp* scp, int32_t* out, uint64_t capacity, uint64_t* count);
+/* Registration::getFitnessScore through pclhip_icp_fitness_score; T NULL: the final transformation of the last alignment. */
+PCLHIP_API pclhip_status pclhip_scp_fitness_score(pclhip_scp* scp, const float T[16], double max_range, double* score,
+                                                 uint64_t* nr);
+/* GPU time (ms) of the feature k-NN, hypothesis and fitness launches of the last pclhip_scp_align. */
+PCLHIP_API void pclhip_scp_last_ms(const pclhip_scp* scp, double* knn_ms, double* hypothesis_ms, double* fitness_ms);
+
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/
  * voxel_grid.hpp:597-814) with downsample_all_data and the optional pass-through filter in front of

@@ -1497,6 +1497,122 @@ class NormalDistributionsTransform : public Registration<PointSource, PointTarge
   bool target_dirty_ = true, source_dirty_ = true;
 };
 
+// pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/include/pcl/registration/
+// sample_consensus_prerejective.h, impl/sample_consensus_prerejective.hpp:78-348) on the C ABI's pclhip_scp: FeatureT is a
+// record of floats (pcl::FPFHSignature33).  The draws are a pure function of (seed, iteration, slot) (include/pclhip.h):
+// setSeed.  An error of :161-212 leaves converged_ false, as the reference's early returns do; lastStatus() tells which.
+template <typename PointSource, typename PointTarget, typename FeatureT>
+class SampleConsensusPrerejective : public Registration<PointSource, PointTarget> {
+  using Base = Registration<PointSource, PointTarget>;
+  static_assert(sizeof(FeatureT) % sizeof(float) == 0 && sizeof(FeatureT) / sizeof(float) <= 64, "FeatureT: at most 64 floats");
+ public:
+  using PointCloudSource = typename Base::PointCloudSource;
+  using Matrix4 = typename Base::Matrix4;
+  using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
+  using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
+  using FeatureCloud = PointCloud<FeatureT>;
+  using FeatureCloudConstPtr = std::shared_ptr<const FeatureCloud>;
+  using Ptr = std::shared_ptr<SampleConsensusPrerejective<PointSource, PointTarget, FeatureT>>;
+  SampleConsensusPrerejective() : SampleConsensusPrerejective(Context::defaultContext()) {}
+  explicit SampleConsensusPrerejective(Context::Ptr ctx) : Base(std::move(ctx)) {  // sample_consensus_prerejective.h:121-131
+    this->reg_name_ = "SampleConsensusPrerejective";
+    pclhip_scp_params_default(&p_);
+    this->max_iterations_ = p_.max_iterations;
+  }
+  ~SampleConsensusPrerejective() override { if (scp_) pclhip_scp_destroy(scp_); }
+
+  void setSourceFeatures(const FeatureCloudConstPtr& features) { input_features_ = features; src_feat_dirty_ = true; }  // :140
+  FeatureCloudConstPtr getSourceFeatures() const { return input_features_; }
+  void setTargetFeatures(const FeatureCloudConstPtr& features) { target_features_ = features; tgt_feat_dirty_ = true; }  // :153
+  FeatureCloudConstPtr getTargetFeatures() const { return target_features_; }
+  void setIndices(const IndicesPtr& indices) override { refuseIndices(indices != nullptr); }
+  void setIndices(const IndicesConstPtr& indices) override { refuseIndices(indices != nullptr); }
+  void setNumberOfSamples(int nr_samples) { p_.nr_samples = nr_samples; }  // :166-194
+  int getNumberOfSamples() const { return p_.nr_samples; }
+  void setCorrespondenceRandomness(int k) { p_.k_correspondences = k; }
+  int getCorrespondenceRandomness() const { return p_.k_correspondences; }
+  void setSimilarityThreshold(float similarity_threshold) { p_.similarity_threshold = similarity_threshold; }  // :203-215
+  float getSimilarityThreshold() const { return p_.similarity_threshold; }
+  void setInlierFraction(float inlier_fraction) { p_.inlier_fraction = inlier_fraction; }  // :221-233
+  float getInlierFraction() const { return p_.inlier_fraction; }
+  void setSeed(std::uint64_t seed) { p_.seed = seed; }
+  std::uint64_t getSeed() const { return p_.seed; }
+  const Indices& getInliers() const { return inliers_; }  // :240
+  const pclhip_scp_result& lastResult() const { return result_; }
+  pclhip_status lastStatus() const { return status_; }
+
+  // Registration::getFitnessScore (impl/registration.hpp:132-168)
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
+    double score = std::numeric_limits<double>::max();
+    if (!this->initCompute() || !ensureScp()) return score;
+    pclhip_scp_fitness_score(scp_, this->final_transformation_.m, max_range, &score, nullptr);
+    return score;
+  }
+
+ protected:
+  void refuseIndices(bool given) {
+    if (given) throw std::logic_error("SampleConsensusPrerejective: source subsets (setIndices) are not supported");
+  }
+  bool ensureScp() {
+    pclhip_index* ix = this->tree_->handle();
+    if (scp_ && (scp_target_ != ix || this->target_built_)) { pclhip_scp_destroy(scp_); scp_ = nullptr; }
+    this->target_built_ = false;
+    if (!scp_) {
+      if ((status_ = pclhip_scp_create(ix, &scp_)) != PCLHIP_OK) return false;
+      scp_target_ = ix;
+      this->source_cloud_updated_ = true;
+      src_feat_dirty_ = tgt_feat_dirty_ = true;
+    }
+    if (this->source_cloud_updated_) {
+      status_ = pclhip_scp_set_source(scp_, this->input_->points.data(), sizeof(PointSource), this->input_->size());
+      if (status_ != PCLHIP_OK) return false;
+      this->source_cloud_updated_ = false;
+    }
+    if (src_feat_dirty_ && input_features_) {
+      status_ = pclhip_scp_set_source_features(scp_, input_features_->points.data(), sizeof(FeatureT), input_features_->size(),
+                                               int(sizeof(FeatureT) / sizeof(float)));
+      if (status_ != PCLHIP_OK) return false;
+      src_feat_dirty_ = false;
+    }
+    if (tgt_feat_dirty_ && target_features_) {
+      status_ = pclhip_scp_set_target_features(scp_, target_features_->points.data(), sizeof(FeatureT), target_features_->size(),
+                                               int(sizeof(FeatureT) / sizeof(float)));
+      if (status_ != PCLHIP_OK) return false;
+      tgt_feat_dirty_ = false;
+    }
+    return true;
+  }
+  void computeTransformation(PointCloudSource& output, const Matrix4& guess) override {  // :157-306
+    this->converged_ = false;
+    inliers_.clear();
+    this->final_transformation_ = guess;
+    if (!ensureScp()) return;
+    p_.max_iterations = this->max_iterations_;
+    p_.max_correspondence_distance = this->corr_dist_threshold_;
+    if ((status_ = pclhip_scp_align(scp_, &p_, guess.m, &result_)) != PCLHIP_OK) return;
+    std::memcpy(this->final_transformation_.m, result_.final_transformation, sizeof result_.final_transformation);
+    this->converged_ = result_.converged != 0;
+    std::uint64_t n = 0;
+    pclhip_scp_inliers(scp_, nullptr, 0, &n);
+    inliers_.resize(n);
+    if (n) pclhip_scp_inliers(scp_, inliers_.data(), n, &n);
+    if (this->converged_) {  // :297-298: the output is written only then
+      output = *this->input_;
+      pclhip_transform_cloud(this->ctx_->get(), this->final_transformation_.m, 1, output.points.data(), output.points.data(),
+                             sizeof(PointSource), output.size(), 0);
+    }
+  }
+
+  pclhip_scp_params p_;
+  pclhip_scp_result result_ = {};
+  pclhip_status status_ = PCLHIP_OK;
+  pclhip_scp* scp_ = nullptr;
+  pclhip_index* scp_target_ = nullptr;
+  FeatureCloudConstPtr input_features_, target_features_;
+  bool src_feat_dirty_ = true, tgt_feat_dirty_ = true;
+  Indices inliers_;
+};
+
 // pcl::io::loadPCDFile / savePCDFile{ASCII,Binary,BinaryCompressed} (io/include/pcl/io/pcd_io.h:685-800)
 // for the point types of this header: records of sizeof(PointT) bytes, normals at +16 when the type has them.
 namespace io {

@@ -9,6 +9,6 @@ from .api import (Communicator, Context, CorrespondenceEstimation, Correspondenc
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
-                  RadiusOutlierRemoval,
+                  RadiusOutlierRemoval, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
-                  default_context, estimateRigidTransformation, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)
+                  default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

@@ -95,6 +95,24 @@ class NdtTrace(C.Structure):
                 ("score", C.c_double), ("transformation", C.c_float * 16)]
 
 
+class ScpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("nr_samples", C.c_int), ("k_correspondences", C.c_int),
+                ("similarity_threshold", C.c_float), ("inlier_fraction", C.c_float),
+                ("max_correspondence_distance", C.c_double), ("seed", C.c_uint64), ("batch_size", C.c_int)]
+
+
+class ScpResult(C.Structure):
+    _fields_ = [("final_transformation", C.c_float * 16), ("converged", C.c_int), ("iterations", C.c_int),
+                ("rejected", C.c_int), ("best_iteration", C.c_int), ("best_error", C.c_float), ("best_count", C.c_uint32),
+                ("trace_count", C.c_int), ("knn_rows", C.c_uint32), ("knn_ms", C.c_double), ("hypothesis_ms", C.c_double),
+                ("fitness_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class ScpTrace(C.Structure):
+    _fields_ = [("iteration", C.c_int), ("rejected", C.c_int), ("samples", C.c_int * 8), ("matches", C.c_int * 8),
+                ("transformation", C.c_float * 16), ("inliers", C.c_uint32), ("error", C.c_float)]
+
+
 NDT_RADIUS, NDT_DIRECT27, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = 0, 1, 2, 3, 4
 
 
@@ -190,6 +208,20 @@ SIGNATURES = {
     "pclhip_ndt_cells": (C.c_int, [_vp, C.POINTER(NdtParams), C.POINTER(_u64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
     "pclhip_ndt_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
                                            C.POINTER(_u64)]),
+    "pclhip_feature_knn": (C.c_int, [_vp, _vp, _sz, _u64, _vp, _sz, _u64, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "pclhip_scp_params_default": (None, [C.POINTER(ScpParams)]),
+    "pclhip_scp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "pclhip_scp_destroy": (None, [_vp]),
+    "pclhip_scp_set_source": (C.c_int, [_vp, _vp, _sz, _u64]),
+    "pclhip_scp_set_source_features": (C.c_int, [_vp, _vp, _sz, _u64, C.c_int]),
+    "pclhip_scp_set_target_features": (C.c_int, [_vp, _vp, _sz, _u64, C.c_int]),
+    "pclhip_scp_set_trace": (C.c_int, [_vp, C.POINTER(ScpTrace), C.c_int]),
+    "pclhip_scp_evaluate": (C.c_int, [_vp, C.POINTER(ScpParams), C.POINTER(C.c_float), C.c_int, _vp, _vp]),
+    "pclhip_scp_align": (C.c_int, [_vp, C.POINTER(ScpParams), C.POINTER(C.c_float), C.POINTER(ScpResult)]),
+    "pclhip_scp_inliers": (C.c_int, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "pclhip_scp_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
+                                           C.POINTER(_u64)]),
+    "pclhip_scp_last_ms": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

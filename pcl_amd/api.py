@@ -2059,3 +2059,253 @@ class FPFHEstimation:
     def computeBoth(self):
         """-> ((m, 33) FPFH, (n, 33) SPFH) of one call."""
         return self._run(True, True)
+
+
+def featureKSearch(ctx, target_rows, query_rows, k):
+    """KdTreeFLANN<FeatureT>::nearestKSearch by exact brute force over pclhip_feature_knn: (n, D) float32 rows, numpy or
+    torch device tensors -> (indices (nq, k) int32, d2 (nq, k) float32, counts (nq,) uint32), ascending (d2, index); -1 /
+    +inf behind the count.  A non-finite target row is never a candidate; a non-finite query row gets count 0."""
+    ctx = ctx or default_context()
+    tp, ts, nt, tk = _cloud_rows(target_rows)
+    qp, qs, nq, qk = _cloud_rows(query_rows)
+    D = tk.shape[1]
+    assert qk.shape[1] == D, "target and query rows of one dimension"
+    idx = np.empty((nq, int(k)), np.int32)
+    d2 = np.empty((nq, int(k)), np.float32)
+    cnt = np.empty(nq, np.uint32)
+    check(ctx.lib.pclhip_feature_knn(ctx.h, tp, ts, nt, qp, qs, nq, D, int(k), C.c_void_p(idx.ctypes.data),
+                                     C.c_void_p(d2.ctypes.data), C.c_void_p(cnt.ctypes.data)), ctx.h)
+    return idx, d2, cnt
+
+
+def _cloud_rows(a):
+    """-> (pointer, stride_bytes, n, keepalive) of (n, D) float32 rows (any D >= 1)."""
+    if _is_torch(a):
+        assert a.dtype.is_floating_point and a.element_size() == 4 and a.dim() == 2
+        a = a.contiguous()
+        return C.c_void_p(a.data_ptr()), a.shape[1] * 4, a.shape[0], a
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert a.ndim == 2
+    return C.c_void_p(a.ctypes.data), a.shape[1] * 4, a.shape[0], a
+
+
+class SampleConsensusPrerejective:
+    """pcl::SampleConsensusPrerejective<PointXYZ, PointXYZ, FeatureT> (registration/include/pcl/registration/
+    sample_consensus_prerejective.h, impl/sample_consensus_prerejective.hpp:78-348) over pclhip_scp_*.  Clouds and features
+    are numpy arrays or torch device tensors; features are (n, D) float32 rows, one per record of their cloud (D = 33:
+    FPFHSignature33).  The draws are a pure function of (seed, iteration, slot) (include/pclhip.h): setSeed."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.p = _lib.ScpParams()
+        self.lib.pclhip_scp_params_default(C.byref(self.p))
+        self.h = None
+        self.tree = None
+        self.src = None
+        self.target = None
+        self.src_features = None
+        self.tgt_features = None
+        self._dirty = dict(tgt=True, src=True, sf=True, tf=True)
+        self.result = None
+        self.trace = []
+        self.ctx._adopt(self)
+
+    def _release(self):
+        self._drop()
+
+    def _drop(self):
+        if getattr(self, "h", None):
+            if self.ctx.h is not None:
+                self.lib.pclhip_scp_destroy(self.h)
+            self.h = None
+        self._dirty = dict(tgt=True, src=True, sf=True, tf=True)
+
+    def getClassName(self):
+        return "SampleConsensusPrerejective"
+
+    # --- inputs (sample_consensus_prerejective.h:136-160, registration.h:195-240) ---
+    def setInputSource(self, cloud):
+        self.src = cloud
+        self._dirty["src"] = True
+
+    def setInputTarget(self, cloud):
+        self.target = cloud
+        self._dirty["tgt"] = True
+
+    def setSearchMethodTarget(self, tree, force_no_recompute=False):
+        """A KdTree over the target (built over the cloud of setInputTarget when none is given)."""
+        self.tree = tree
+        self._dirty["tgt"] = True
+
+    def setSourceFeatures(self, features):
+        self.src_features = features
+        self._dirty["sf"] = True
+
+    def getSourceFeatures(self):
+        return self.src_features
+
+    def setTargetFeatures(self, features):
+        self.tgt_features = features
+        self._dirty["tf"] = True
+
+    def getTargetFeatures(self):
+        return self.tgt_features
+
+    def setIndices(self, indices):
+        if indices is not None:
+            raise NotImplementedError("SampleConsensusPrerejective: source subsets (setIndices) are not supported")
+
+    def setCommunicator(self, comm):
+        raise NotImplementedError("SampleConsensusPrerejective: multi-GPU registration is not supported")
+
+    # --- parameters (:162-232) ---
+    def setNumberOfSamples(self, nr_samples):
+        self.p.nr_samples = int(nr_samples)
+
+    def getNumberOfSamples(self):
+        return int(self.p.nr_samples)
+
+    def setCorrespondenceRandomness(self, k):
+        self.p.k_correspondences = int(k)
+
+    def getCorrespondenceRandomness(self):
+        return int(self.p.k_correspondences)
+
+    def setSimilarityThreshold(self, similarity_threshold):
+        self.p.similarity_threshold = float(similarity_threshold)
+
+    def getSimilarityThreshold(self):
+        return float(self.p.similarity_threshold)
+
+    def setInlierFraction(self, inlier_fraction):
+        self.p.inlier_fraction = float(inlier_fraction)
+
+    def getInlierFraction(self):
+        return float(self.p.inlier_fraction)
+
+    def setMaximumIterations(self, n):
+        self.p.max_iterations = int(n)
+
+    def getMaximumIterations(self):
+        return int(self.p.max_iterations)
+
+    def setMaxCorrespondenceDistance(self, d):
+        self.p.max_correspondence_distance = float(d)
+
+    def getMaxCorrespondenceDistance(self):
+        return float(self.p.max_correspondence_distance)
+
+    def setSeed(self, seed):
+        self.p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def getSeed(self):
+        return int(self.p.seed)
+
+    def setBatchSize(self, n):
+        """Iterations per batch of launches; never changes a result."""
+        self.p.batch_size = int(n)
+
+    def _ensure(self):
+        if self.target is None and (self.tree is None or self.tree.h is None):
+            raise ValueError("No input target dataset was given!")
+        if self.src is None:
+            raise ValueError("No input source dataset was given!")
+        if self._dirty["tgt"]:
+            if self.h is not None:
+                self._drop()
+            if self.tree is None:
+                self.tree = KdTree(self.ctx)
+            if self.target is not None and (self.tree.h is None or self.tree._cloud_id != (id(self.target), None)):
+                self.tree.setInputCloud(self.target)
+            h = C.c_void_p()
+            check(self.lib.pclhip_scp_create(self.tree.h, C.byref(h)), self.ctx.h)
+            self.h = h
+            self._dirty["tgt"] = False
+        if self._dirty["src"]:
+            ptr, stride, n, keep = _cloud(self.src)
+            check(self.lib.pclhip_scp_set_source(self.h, ptr, stride, n), self.ctx.h)
+            self._dirty["src"] = False
+        for key, rows, fn in (("sf", self.src_features, self.lib.pclhip_scp_set_source_features),
+                              ("tf", self.tgt_features, self.lib.pclhip_scp_set_target_features)):
+            if self._dirty[key] and rows is not None:
+                ptr, stride, n, keep = _cloud_rows(rows)
+                check(fn(self.h, ptr, stride, n, int(keep.shape[1])), self.ctx.h)
+                self._dirty[key] = False
+
+    def align(self, guess=None, trace_capacity=0, want_output=False):
+        """Registration::align -> computeTransformation (:157-306).  Returns the registered source (the input moved by the
+        final transformation, transformPointCloud's order) when want_output and the alignment converged, else None; with
+        trace_capacity > 0 one dict per iteration in self.trace (samples, matches, rejected, transformation, inliers,
+        error)."""
+        self._ensure()
+        cap = int(trace_capacity)
+        buf = (_lib.ScpTrace * max(1, cap))()
+        check(self.lib.pclhip_scp_set_trace(self.h, buf, cap), self.ctx.h)
+        r = _lib.ScpResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16)
+        try:
+            check(self.lib.pclhip_scp_align(self.h, C.byref(self.p), _fp(g) if g is not None else None, C.byref(r)),
+                  self.ctx.h)
+        finally:
+            self.lib.pclhip_scp_set_trace(self.h, None, 0)
+        self.result = r
+        ns = int(self.p.nr_samples)
+        self.trace = [dict(iteration=int(t.iteration), rejected=int(t.rejected), samples=list(t.samples)[:ns],
+                           matches=list(t.matches)[:ns], transformation=np.array(t.transformation, np.float32).reshape(4, 4),
+                           inliers=int(t.inliers), error=np.float32(t.error)) for t in buf[:r.trace_count]]
+        if not want_output or not r.converged:
+            return None
+        ptr, stride, n, keep = _cloud(self.src)
+        out = keep.clone() if _is_torch(self.src) else keep.copy()
+        optr = C.c_void_p(out.data_ptr() if _is_torch(self.src) else out.ctypes.data)
+        check(self.lib.pclhip_transform_cloud(self.ctx.h, _fp(np.ascontiguousarray(self.getFinalTransformation()).reshape(16)),
+                                              1, ptr, optr, stride, n, 0), self.ctx.h)
+        return out
+
+    def evaluate(self, transforms):
+        """getFitness (:310-348) of (H, 4, 4) transforms in batched launches -> (counts (H,) uint32, errors (H,) float32)."""
+        self._ensure()
+        T = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
+        cnt = np.zeros(len(T), np.uint32)
+        err = np.zeros(len(T), np.float32)
+        check(self.lib.pclhip_scp_evaluate(self.h, C.byref(self.p), _fp(T), len(T), C.c_void_p(cnt.ctypes.data),
+                                           C.c_void_p(err.ctypes.data)), self.ctx.h)
+        return cnt, err
+
+    def getFinalTransformation(self):
+        return np.array(self.result.final_transformation, np.float32).reshape(4, 4)
+
+    def hasConverged(self):
+        return bool(self.result.converged)
+
+    def getInliers(self):
+        """The accepted hypothesis' inlier indices into the source, ascending (empty when nothing was accepted)."""
+        n = C.c_uint64(0)
+        check(self.lib.pclhip_scp_inliers(self.h, None, 0, C.byref(n)), self.ctx.h)
+        out = np.zeros(int(n.value), np.int32)
+        if len(out):
+            check(self.lib.pclhip_scp_inliers(self.h, C.c_void_p(out.ctypes.data), len(out), C.byref(n)), self.ctx.h)
+        return out
+
+    def getFitnessScore(self, max_range=float(np.finfo(np.float64).max)):
+        """Registration::getFitnessScore (impl/registration.hpp:132-168) with the final transformation."""
+        self._ensure()
+        T = np.ascontiguousarray(self.getFinalTransformation(), np.float32).reshape(16)
+        score = C.c_double(0.0)
+        nr = C.c_uint64(0)
+        check(self.lib.pclhip_scp_fitness_score(self.h, _fp(T), C.c_double(max_range), C.byref(score), C.byref(nr)),
+              self.ctx.h)
+        return float(score.value)
+
+    def lastMs(self):
+        """GPU time (ms) of the feature k-NN, hypothesis and fitness launches of the last align()."""
+        a, b, c = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self.lib.pclhip_scp_last_ms(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
