@@ -271,7 +271,9 @@ PCLHIP_API pclhip_status pclhip_radius_outlier_removal(pclhip_index* index, cons
  * impl/fpfh.hpp:51-303, pcl::computePairFeatures of features/src/pfh.cpp:45-103): search surface == input, 11 / 11 / 11
  * bins.  `index` is built over the whole unscaled cloud and holds normals (pclhip_normals* or pclhip_index_set_normals):
  * PCLHIP_ERR_STATE without them; radius <= 0 is PCLHIP_ERR_INVALID.  The neighbourhood is every indexed point with float
- * d2 < float(radius * radius), the point itself included (as pclhip_radius_search).
+ * d2 < float(radius * radius), the point itself included (as pclhip_radius_search).  A positive radius whose float square
+ * is 0 (below about 2.6e-23) is a valid call in which no point has a neighbour, not even itself, as in the reference:
+ * every SPFH row of a point with a finite normal is all-zero, every FPFH row is NaN and counted in out_nan_count.
  *   out       (host or device) 33 floats (f1, f2, f3 histograms) at byte 0 of each out_stride_bytes record, one per query:
  *             every record of the cloud, or indices[0..n_indices) in that order
  *   out_spfh  (host or device, optional) the 33-float SPFH rows (computePointSPFHSignature), dense, one per ORIGINAL

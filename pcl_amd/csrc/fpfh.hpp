@@ -1,7 +1,10 @@
 // fpfh.hpp -- FPFHEstimation with setRadiusSearch over the index (included by radius.hip).
 // Replaces pcl::FPFHEstimation<PointInT, PointNT, PointOutT>::computeFeature (features/include/pcl/features/impl/fpfh.hpp
 // :51-303) with pcl::computePairFeatures (features/src/pfh.cpp:45-103): the search surface is the input, the
-// neighbourhood every indexed point with float d2 < float(r * r), 11 / 11 / 11 bins.
+// neighbourhood every indexed point with float d2 < float(r * r), 11 / 11 / 11 bins.  A positive r whose float square
+// is 0 gives every point an EMPTY neighbourhood (d2 < 0 never holds, not even for the point itself): the reference then
+// leaves the SPFH row at zero (fpfh.hpp:224-225) and writes a NaN FPFH row (:255-261), and so do the two kernels -- without
+// a walk, the bound is the same for every point.
 //
 // Pipeline (one stream, one read-back at the end):
 //   outlier_pos_kernel   (with indices only) entry -> sorted position, marked and compacted so the queries run in kd order
@@ -191,15 +194,17 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_spfh_kernel(IndexView ix, float
 #pragma unroll
     for (int b = 0; b < FPFH_DIM; ++b) pol.col[b * WAVE] = 0;
     const uint32_t start = uniform_u32(pos / LEAF);  // lane 0 always holds a point
-    traverse<FpfhSpfh, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
+    if (t > 0.0f)  // (t == 0: nothing lies within d2 < 0, the counters stay at zero)
+      traverse<FpfhSpfh, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
     if (!real) continue;
     float* row = spfh + size_t(pos) * FPFH_DIM;
     if (!fin) {
       for (int b = 0; b < FPFH_DIM; ++b) row[b] = __builtin_nanf("");
       continue;
     }
-    if (pol.cnt - 1u > FPFH_MAX_COUNT) *overflow = 1u;  // a bin may have wrapped: the call fails
-    const float incr = __fdiv_rn(100.0f, float(pol.cnt - 1u));  // fpfh.hpp:77 (inf for a lone point: never added)
+    const uint32_t others = pol.cnt > 0u ? pol.cnt - 1u : 0u;  // (cnt == 0 only with t == 0: the point misses itself)
+    if (others > FPFH_MAX_COUNT) *overflow = 1u;  // a bin may have wrapped: the call fails
+    const float incr = __fdiv_rn(100.0f, float(others));  // fpfh.hpp:77 (inf for a lone point: never added)
     for (int b = 0; b < FPFH_DIM; ++b) {
       const uint32_t c = pol.col[b * WAVE];
       float v = 0.0f;
@@ -266,6 +271,11 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_weight_kernel(IndexView ix, con
 #pragma unroll
     for (int b = 0; b < FPFH_DIM; ++b) pol.acc[b] = 0.0;
     const uint32_t start = uniform_u32(pos / LEAF);  // lane 0 always holds a query
+    if (!(t > 0.0f)) {  // no neighbour, not even the query itself: the reference divides by the sum of no weights
+      if (real)
+        for (int b = 0; b < FPFH_DIM; ++b) fpfh[size_t(pos) * FPFH_DIM + b] = __builtin_nanf("");
+      continue;
+    }
     traverse<FpfhWeight, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
     if (!real) continue;
     float* row = fpfh + size_t(pos) * FPFH_DIM;

@@ -20,7 +20,11 @@ Besides the float32 result, restate() returns
             histogram, not rounded
 Deviation restated as pclhip_fpfh documents it: a point whose own normal is not finite gets NaN rows; a neighbour whose
 normal is not finite is skipped in both passes but counts towards hist_incr.  Non-finite points are no one's neighbours
-and get NaN rows."""
+and get NaN rows.
+
+A radius whose float32 square is 0 finds no neighbour at all, not even the point itself (d2 < 0 never holds): the SPFH
+row stays at zero (fpfh.hpp:224-225) and weightPointSPFHSignature divides by the sum of no weights: the FPFH row is NaN
+(fpfh.hpp:255-261).  restate() and weigh() give both."""
 import math
 import os
 
@@ -164,18 +168,36 @@ def weigh(spfh, points, radius, hoods=None):
     m = np.zeros(n, np.int64)
     for i, (nb, d2) in hoods.items():
         m[i] = len(nb)
-        if np.isnan(spfh[i, 0]):
+        if np.isnan(spfh[i, 0]) or len(nb) == 0:  # no neighbour, not even itself (float32(r * r) == 0): NaN
             continue
         f32[i] = weight_float32(spfh, nb, d2)
         f64[i] = weight_float64(spfh, nb, d2)
     return f32, f64, m
 
 
-def restate(points, normals, radius):
+def neighbourhoods_of(points, radius, rows):
+    """neighbourhoods() of the finite records `rows` alone, each by one pass over the cloud"""
+    pts = np.asarray(points, np.float32)
+    ids = np.nonzero(np.isfinite(pts).all(axis=1))[0]
+    p = pts[ids]
+    t = F32(float(radius) * float(radius))
+    out = {}
+    for i in rows:
+        dx, dy, dz = pts[i, 0] - p[:, 0], pts[i, 1] - p[:, 1], pts[i, 2] - p[:, 2]
+        d2 = (dx * dx + dy * dy) + dz * dz
+        sel = np.nonzero(d2 < t)[0]
+        order = np.lexsort((ids[sel], d2[sel]))
+        out[int(i)] = (ids[sel][order], d2[sel][order])
+    return out
+
+
+def restate(points, normals, radius, hoods=None):
+    """hoods (optional): the neighbourhoods of the points to restate (neighbourhoods_of).  The SPFH part of the result is
+    then that of these points alone, and fpfh32 / fpfh64 mean nothing (they weigh rows that were not restated)."""
     pts = np.asarray(points, np.float32)
     nrm = np.asarray(normals, np.float32)[:, :3]
     n = pts.shape[0]
-    hoods = neighbourhoods(pts, radius)
+    hoods = hoods if hoods is not None else neighbourhoods(pts, radius)
     nfin = np.isfinite(nrm).all(axis=1)
     counts = np.zeros((n, 3 * BINS), np.int64)
     counts64 = np.zeros((n, 3 * BINS), np.int64)
@@ -205,7 +227,7 @@ def restate(points, normals, radius):
             for h in range(3):
                 counts[i, h * BINS:(h + 1) * BINS] = np.bincount(b32[:, h], minlength=BINS)
                 counts64[i, h * BINS:(h + 1) * BINS] = np.bincount(b64[:, h], minlength=BINS)
-        spfh[i] = spfh_values(counts[i], len(nb))
+        spfh[i] = spfh_values(counts[i], len(nb)) if len(nb) else 0.0  # (no neighbour at all: nothing was added)
     fpfh32, fpfh64, m = weigh(spfh, pts, radius, hoods)
     return dict(spfh=spfh, counts=counts, counts64=counts64, unstable=unstable, disagree=disagree, pairs=pairs,
                 fpfh32=fpfh32, fpfh64=fpfh64, m=m, hoods=hoods)
@@ -217,9 +239,9 @@ def counts_from_rows(rows, m):
     rows = np.asarray(rows, np.float32)
     out = np.full(rows.shape, -1, np.int64)
     for i in range(rows.shape[0]):
-        if np.isnan(rows[i, 0]) or m[i] < 1:
+        if np.isnan(rows[i, 0]):
             continue
-        k = int(m[i]) - 1
+        k = max(int(m[i]) - 1, 0)  # (m == 0: float32(r * r) == 0, not even the point itself)
         tab = spfh_values(np.arange(k + 1), int(m[i])) if k > 0 else np.zeros(1, np.float32)
         for b in range(rows.shape[1]):
             hit = np.nonzero(tab == rows[i, b])[0]

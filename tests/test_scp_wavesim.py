@@ -1,5 +1,6 @@
 """SampleConsensusPrerejective in the CPU tier: the `-m gpu` tests of tests/test_gpu_scp.py and the C++ mirror's bunny test
-(tests/test_gpu_scp_cpp.py) run on the wavefront emulation of tests/wavesim (the recipe of tests/test_wavesim.py:
+(tests/test_gpu_scp_cpp.py) and the regimes of tests/test_gpu_scp_regimes.py
+run on the wavefront emulation of tests/wavesim (the recipe of tests/test_wavesim.py:
 PCLHIP_LIB = the emulation, PCLHIP_ALLOW_WAVESIM=1, in a subprocess).  Nothing is deselected: every shape there is small."""
 import os
 import shutil
@@ -25,7 +26,8 @@ def wavesim_lib():
 def test_scp_gpu_tests_on_the_emulation(wavesim_lib):
     env = dict(os.environ, PCLHIP_LIB=wavesim_lib, PCLHIP_ALLOW_WAVESIM="1")
     cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
-           os.path.join(ROOT, "tests", "test_gpu_scp.py"), os.path.join(ROOT, "tests", "test_gpu_scp_cpp.py")]
+           os.path.join(ROOT, "tests", "test_gpu_scp.py"), os.path.join(ROOT, "tests", "test_gpu_scp_cpp.py"),
+           os.path.join(ROOT, "tests", "test_gpu_scp_regimes.py")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
     tail = r.stdout[-3000:] + "\n" + r.stderr[-3000:]
     assert r.returncode == 0, tail
