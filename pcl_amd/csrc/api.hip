@@ -378,13 +378,14 @@ __global__ void transform_cloud_kernel(Mat44 T, int order, const void* in, void*
 }
 
 // dense per-original-source arrays of the last iteration's matches
-__global__ void scatter_matches_kernel(const float4* __restrict__ cur, const uint32_t* __restrict__ match,
-                                       const float* __restrict__ d2, const uint8_t* __restrict__ keep, uint32_t n,
+__global__ void scatter_matches_kernel(const float4* __restrict__ cur, const float4* __restrict__ tgt_pts,
+                                       const uint32_t* __restrict__ match_pos, const float* __restrict__ d2,
+                                       const uint8_t* __restrict__ keep, uint32_t n,
                                        int32_t* __restrict__ out_m, float* __restrict__ out_d) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t oq = __float_as_uint(cur[i].w);
-  const uint32_t m = match[i];
+  const uint32_t m = match_index_at(tgt_pts, match_pos[i]);
   const bool kept = m != NO_INDEX && (keep == nullptr || keep[i]);
   out_m[oq] = kept ? int32_t(m) : -1;
   out_d[oq] = d2[i];
@@ -1446,14 +1447,12 @@ static void icp_free_source(pclhip_icp* icp) {
   if (icp->src_nrm_sorted0) (void)dev_free(icp->ctx, icp->src_nrm_sorted0);
   if (icp->src_nrm_cur) (void)dev_free(icp->ctx, icp->src_nrm_cur);
   icp->src_nrm_sorted0 = icp->src_nrm_cur = nullptr;
-  if (icp->match) (void)dev_free(icp->ctx, icp->match);
   if (icp->match_pos) (void)dev_free(icp->ctx, icp->match_pos);
   if (icp->keep) (void)dev_free(icp->ctx, icp->keep);
   icp->keep = nullptr;
   if (icp->match_d2) (void)dev_free(icp->ctx, icp->match_d2);
   if (icp->partials) (void)dev_free(icp->ctx, icp->partials);
   icp->src_sorted0 = icp->src_cur = nullptr;
-  icp->match = nullptr;
   icp->match_pos = nullptr;
   icp->match_d2 = nullptr;
   icp->partials = nullptr;
@@ -1542,7 +1541,6 @@ pclhip_status pclhip_icp_set_source_indexed(pclhip_icp* icp, const void* points,
   icp->grid_blocks = icp_grid_blocks(ctx, icp->n);
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->src_sorted0, cap * sizeof(float4)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->src_cur, cap * sizeof(float4)));
-  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->match, cap * sizeof(uint32_t)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->match_pos, cap * sizeof(uint32_t)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->match_d2, cap * sizeof(float)));
   PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->partials, size_t(icp->grid_blocks) * PCLHIP_ICP_NSUMS * sizeof(double)));
@@ -1863,8 +1861,8 @@ pclhip_status pclhip_icp_fetch_correspondence_records(pclhip_icp* icp, void* out
   hipStream_t s = ctx->stream;
   PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(dm, 0xFF, no * sizeof(int32_t), s));
   PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(tot, 0, 4 * sizeof(uint32_t), s));
-  hipLaunchKernelGGL(scatter_matches_kernel, dim3((icp->n + 255) / 256), dim3(256), 0, s, icp->src_cur, icp->match, icp->match_d2,
-                     filtered ? icp->keep : nullptr, icp->n, dm, dd);
+  hipLaunchKernelGGL(scatter_matches_kernel, dim3((icp->n + 255) / 256), dim3(256), 0, s, icp->src_cur, icp->target->pts,
+                     icp->match_pos, icp->match_d2, filtered ? icp->keep : nullptr, icp->n, dm, dd);
   const unsigned blocks = unsigned((no + 255) / 256);
   hipLaunchKernelGGL(match_flag_kernel, dim3(blocks), dim3(256), 0, s, dm, uint64_t(no), flag);
   launch_scan_u32(s, flag, no, partial, tot, pos);
@@ -1909,7 +1907,7 @@ pclhip_status pclhip_icp_fetch_correspondences(pclhip_icp* icp, int32_t* index_q
   PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(dm, 0xFF, no * sizeof(int32_t), ctx->stream));
   const bool filtered = icp->reciprocal || !icp->rejectors.empty();
   hipLaunchKernelGGL(scatter_matches_kernel, dim3((icp->n + 255) / 256), dim3(256), 0, ctx->stream, icp->src_cur,
-                     icp->match, icp->match_d2, filtered ? icp->keep : nullptr, icp->n, dm, dd);
+                     icp->target->pts, icp->match_pos, icp->match_d2, filtered ? icp->keep : nullptr, icp->n, dm, dd);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   std::vector<int32_t> hm(no);
   std::vector<float> hd(no);

@@ -75,7 +75,6 @@ __global__ __launch_bounds__(BLOCK) void gicp_move_kernel(const float4* __restri
 // the pairs of an outer iteration (impl/gicp.hpp:858-876) and the x-independent sums of dfddf (:660-679)
 __global__ __launch_bounds__(BLOCK) void gicp_pack_kernel(IndexView ix, const float4* __restrict__ moved, uint32_t n,
                                                           const uint32_t* __restrict__ match_pos,
-                                                          const uint32_t* __restrict__ match,
                                                           const double* __restrict__ src_cov,
                                                           const double* __restrict__ tgt_cov, GicpR R,
                                                           double* __restrict__ mstore, GicpPair* __restrict__ pairs,
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_pack_kernel(IndexView ix, const fl
     const float4 p = moved[i];
     const float4 q = ix.pts[pos];
     const double* c1 = src_cov + size_t(__float_as_uint(p.w)) * 9;
-    const double* c2 = tgt_cov + size_t(match[i]) * 9;
+    const double* c2 = tgt_cov + size_t(__float_as_uint(q.w)) * 9;  // the match's original index rides in its point
     double C1[9], C2[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
@@ -492,7 +491,7 @@ pclhip_status pclhip_gicp_align(pclhip_gicp* G, const pclhip_gicp_params* P, con
     if (n > 0) {
       (void)hipEventRecord(G->ev_a, ctx->stream);
       hipLaunchKernelGGL(gicp_pack_kernel, dim3(G->sums.blocks), dim3(BLOCK), 0, ctx->stream, G->target->view(), G->moved, n,
-                         icp->match_pos, icp->match, G->src_cov, G->tgt_cov, R, G->mstore, static_cast<GicpPair*>(G->pairs),
+                         icp->match_pos, G->src_cov, G->tgt_cov, R, G->mstore, static_cast<GicpPair*>(G->pairs),
                          G->sums.partials);
       PCLHIP_CHECK_HIP(ctx, hipGetLastError());
       st = G->sums.read(ctx, gf::kGicpCached, G->cached, G->ev_b);

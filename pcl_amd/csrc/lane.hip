@@ -3,7 +3,7 @@
 // Replaces, for every launch that is not the first of an alignment, the wave-cooperative icp_search_body of search.hip
 // inside CorrespondenceEstimation::determineCorrespondences
 // (registration/include/pcl/registration/impl/correspondence_estimation.hpp:145-218): same inputs (the working cloud,
-// the previous matches as seeds), same outputs (match / match_pos / match_d2), bit for bit.  Three launches:
+// the previous matches as seeds), same outputs (match_pos / match_d2), bit for bit.  Three launches:
 //
 //   icp_lane_resolve_kernel   every source point: move it, evaluate its seed's leaf (a seed that is far away -- the
 //                             second iteration of an alignment slides every query tens of point spacings along the
@@ -45,7 +45,7 @@ __device__ __forceinline__ void lane_stat(unsigned long long* g, int slot, bool 
 __global__ __launch_bounds__(LBLOCK, PCLHIP_LANE_MINW) void icp_lane_resolve_kernel(
     const float4* __restrict__ pts, const float* __restrict__ soa, LaneTree lt, float4* __restrict__ cur, uint32_t ns, Mat34 T,
     const IcpControl* __restrict__ ctl, RegionBox region, int order, float bound, int use_max, float far2, int max_up,
-    uint32_t* __restrict__ match_pos, uint32_t* __restrict__ match, float* __restrict__ match_d2,
+    uint32_t* __restrict__ match_pos, float* __restrict__ match_d2,
     unsigned long long* __restrict__ qmask, uint32_t* __restrict__ block_count, unsigned long long* gstats) {
   if (ctl != nullptr) {
     if (ctl->stop != 0 || ctl->restart != 0) return;  // ended / the launch that starts an alignment: not ours
@@ -99,10 +99,7 @@ __global__ __launch_bounds__(LBLOCK, PCLHIP_LANE_MINW) void icp_lane_resolve_ker
   }
   if (in_range) {
     if (!gave_up) {
-      const bool found = valid && pos != NO_INDEX;
-      uint32_t mid = NO_INDEX;
-      if (found) mid = __float_as_uint(pos == sp ? t0.w : pts[pos].w);
-      match[i] = found ? mid : NO_INDEX;
+      const bool found = valid && pos != NO_INDEX;  // (its original index: match_index_at, for whoever wants it)
       match_pos[i] = found ? pos : NO_INDEX;
       match_d2[i] = found ? fast.best[0] : __builtin_inff();
     } else if (pos != NO_INDEX) {
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(LBLOCK) void icp_lane_finish_kernel(const float4* _
                                                                  LaneTree lt, const float4* __restrict__ cur,
                                                                  const IcpControl* __restrict__ ctl, float bound, int use_max,
                                                                  float far2, uint32_t* __restrict__ match_pos,
-                                                                 uint32_t* __restrict__ match, float* __restrict__ match_d2,
+                                                                 float* __restrict__ match_d2,
                                                                  const uint32_t* __restrict__ queue,
                                                                  const uint32_t* __restrict__ tot, unsigned long long* gstats) {
   if (ctl != nullptr && (ctl->stop != 0 || ctl->restart != 0)) return;
@@ -219,7 +216,6 @@ __global__ __launch_bounds__(LBLOCK) void icp_lane_finish_kernel(const float4* _
     pol.leaf_global(soa, home, qx, qy, qz);
     (void)lane_search(lt, soa, p.x, p.y, p.z, pol, home, 64);
     const bool found = pol.pos != NO_INDEX;
-    match[i] = found ? key_index(pol.key) : NO_INDEX;
     match_pos[i] = found ? pol.pos : NO_INDEX;
     match_d2[i] = found ? key_dist(pol.key) : __builtin_inff();
     ++served;
@@ -275,14 +271,14 @@ pclhip_status launch_lane_search(pclhip_icp* icp, const float T12[12], const Icp
   // a seed farther than this (squared) is no seed: the lane looks for a leaf next to the query instead
   const float far2 = ctx->opt_lane_far * ix->leaf_diag2;
   hipLaunchKernelGGL(icp_lane_resolve_kernel, dim3(nblocks), dim3(LBLOCK), 0, s, ix->pts, ix->soa, lt, icp->src_cur, icp->n, M,
-                     ctl, icp->region, order, bound, use_max ? 1 : 0, far2, ctx->opt_lane_max_up, icp->match_pos, icp->match,
+                     ctl, icp->region, order, bound, use_max ? 1 : 0, far2, ctx->opt_lane_max_up, icp->match_pos,
                      icp->match_d2, icp->lane_mask, icp->lane_bcount, ctx->stats);
   hipLaunchKernelGGL(icp_lane_queue_kernel, dim3((ngroups + LQ_CHUNK - 1) / LQ_CHUNK), dim3(LBLOCK), 0, s, ctl, icp->lane_mask,
                      icp->lane_bcount, ngroups, nblocks, icp->lane_queue, icp->lane_tot);
   uint32_t gf = uint32_t(ctx->num_cus) * 8u;
   if (gf > nblocks) gf = nblocks;
   hipLaunchKernelGGL(icp_lane_finish_kernel, dim3(gf), dim3(LBLOCK), 0, s, ix->pts, ix->soa, lt, icp->src_cur, ctl, bound,
-                     use_max ? 1 : 0, far2, icp->match_pos, icp->match, icp->match_d2, icp->lane_queue, icp->lane_tot,
+                     use_max ? 1 : 0, far2, icp->match_pos, icp->match_d2, icp->lane_queue, icp->lane_tot,
                      ctx->stats);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   return PCLHIP_OK;

@@ -109,6 +109,21 @@ struct RegionBox {
   int on;
 };
 
+#if defined(__HIPCC__) || defined(PCLHIP_WAVESIM)  // device helpers (host-only units include this file too)
+// The group counters written back to zero by a kernel that runs behind the one that used them (PCLHIP_LAUNCH_REARM below):
+// eight plain stores from the first lanes of block 0, visible to the next kernel of the stream when this one ends.
+__device__ __forceinline__ void sched_ctr_rearm(uint32_t* __restrict__ ctr) {
+  if (ctr != nullptr && blockIdx.x == 0 && threadIdx.x < 8u) ctr[threadIdx.x * uint32_t(SCHED_CTR_STRIDE)] = 0u;
+}
+
+// The ORIGINAL index of the target point at sorted position `pos` (NO_INDEX: no match).  The ICP search kernels leave the
+// matches as positions only (pclhip_icp::match_pos); whoever needs the original index -- the correspondence fetch, the
+// OneToOne rejector, GICP's pair packing -- reads it here, where it reads the pair anyway.
+__device__ __forceinline__ uint32_t match_index_at(const float4* __restrict__ pts, uint32_t pos) {
+  return pos != NO_INDEX ? __float_as_uint(pts[pos].w) : NO_INDEX;
+}
+#endif
+
 // Device-resident state of the ICP loop (icp_loop.hip): the iteration is closed on the GPU
 // (icp_solve_kernel), so consecutive iterations are queued back to back and the host only observes.
 struct IcpControl {
@@ -195,6 +210,8 @@ struct pclhip_ctx {
   unsigned long long* stats = nullptr;  // 8 work counters (device), non-null when enabled
   uint32_t* sched_ctr = nullptr;        // 8 group counters (device), 128 bytes apart: the dynamic tail of GroupFeed
   std::mutex feed_mutex;                // keeps "zero the counters, launch" one step of the stream (PCLHIP_LAUNCH_FED)
+  bool sched_ctr_zero = true;           // under feed_mutex: in stream order the counters are zero behind everything queued so
+                                        // far (pclhip_ctx_create zeroes them; PCLHIP_LAUNCH_FED / PCLHIP_LAUNCH_REARM keep it)
   void* staging = nullptr;  // device staging for host inputs
   size_t staging_bytes = 0;
   // Device allocations of indices, registrations and temporaries are recycled through the context
@@ -290,8 +307,8 @@ struct pclhip_icp {
   float4* src_nrm_sorted0 = nullptr;  // source normals in the same order (symmetric objective), pristine
   float4* src_nrm_cur = nullptr;      // ... rotated along with the working copy
   bool enforce_same_direction_normals = true;  // icp.h:368
-  uint32_t* match = nullptr;       // per sorted source slot: ORIGINAL target index or NO_INDEX
-  uint32_t* match_pos = nullptr;   // ... and its sorted position (seed of the next iteration)
+  uint32_t* match_pos = nullptr;   // per sorted source slot: sorted position of the matched target point or NO_INDEX (seed of
+                                   // the next iteration; its ORIGINAL index is read on demand: match_index_at)
   float* match_d2 = nullptr;
   bool seeds_cleared = false;       // match_pos was just reset (pclhip_icp_reset): the next host-driven launch is a cold one
   double* partials = nullptr;      // [blocks][NSUMS]
@@ -495,12 +512,29 @@ pclhip_status sharded_filters_ok(pclhip_icp* icp);
 #endif
 
 // Kernels that take part of their groups from the context's counters (traverse.hpp: GroupFeed) are launched through
-// this: the counters are zeroed in stream order first, and no other thread's launch gets between the two.
+// this.  The invariant: in stream order the counters are zero whenever such a kernel starts.  Whoever dirtied them last leaves
+// them zero, and the host knows (pclhip_ctx::sched_ctr_zero, under feed_mutex, so no other thread's launch gets in between):
+//   PCLHIP_LAUNCH_FED    zeroes them first (a memset on the stream) unless they are known to be zero, launches, and marks them
+//                        dirty -- k-NN, normals, radius, outlier, FPFH, GICP covariances, the reciprocal search, the fitness
+//                        score and every ICP search launch;
+//   PCLHIP_LAUNCH_REARM  launches a kernel that starts behind the fed one and writes the zeros back itself (sched_ctr_rearm),
+//                        and marks them zero: the kernel that closes an ICP iteration (search.hip: icp_finalize_kernel), so a
+//                        queue of iterations carries no memset launch at all.
+// A fed kernel that falls through (the device-driven loop's launches behind a finished alignment) takes no ticket, and the
+// closing kernel re-arms before it looks at the stop flag: the counters are zero behind such a step as well.
 #define PCLHIP_LAUNCH_FED(ctx, ...)                                                                \
   do {                                                                                             \
     std::lock_guard<std::mutex> pclhip_feed_lock((ctx)->feed_mutex);                               \
-    (void)hipMemsetAsync((ctx)->sched_ctr, 0, pclhip::SCHED_CTR_BYTES, (ctx)->stream);             \
+    if (!(ctx)->sched_ctr_zero)                                                                    \
+      (void)hipMemsetAsync((ctx)->sched_ctr, 0, pclhip::SCHED_CTR_BYTES, (ctx)->stream);           \
     hipLaunchKernelGGL(__VA_ARGS__);                                                               \
+    (ctx)->sched_ctr_zero = false;                                                                 \
+  } while (0)
+#define PCLHIP_LAUNCH_REARM(ctx, ...)                                                              \
+  do {                                                                                             \
+    std::lock_guard<std::mutex> pclhip_feed_lock((ctx)->feed_mutex);                               \
+    hipLaunchKernelGGL(__VA_ARGS__);                                                               \
+    (ctx)->sched_ctr_zero = true;                                                                  \
   } while (0)
 
 // ---- kernels launched from api.cpp ----------------------------------------------------------

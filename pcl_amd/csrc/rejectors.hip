@@ -379,22 +379,24 @@ __global__ void rej_trim_kernel(const float4* __restrict__ cur, const float* __r
 }
 
 // correspondence_rejection_one_to_one.cpp:49-65: per match index the smallest (distance, query) wins
-__global__ void rej_o2o_min_kernel(const float4* __restrict__ cur, const uint32_t* __restrict__ match,
+__global__ void rej_o2o_min_kernel(const float4* __restrict__ cur, const float4* __restrict__ tgt_pts,
+                                   const uint32_t* __restrict__ match_pos,
                                    const float* __restrict__ d2, const uint8_t* __restrict__ keep, uint32_t n,
                                    unsigned long long* __restrict__ best) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && keep[i]) {
     const unsigned long long k = (uint64_t(__float_as_uint(d2[i])) << 32) | __float_as_uint(cur[i].w);
-    atomicMin(best + match[i], k);
+    atomicMin(best + match_index_at(tgt_pts, match_pos[i]), k);
   }
 }
-__global__ void rej_o2o_keep_kernel(const float4* __restrict__ cur, const uint32_t* __restrict__ match,
+__global__ void rej_o2o_keep_kernel(const float4* __restrict__ cur, const float4* __restrict__ tgt_pts,
+                                    const uint32_t* __restrict__ match_pos,
                                     const float* __restrict__ d2, uint32_t n,
                                     const unsigned long long* __restrict__ best, uint8_t* __restrict__ keep) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && keep[i]) {
     const unsigned long long k = (uint64_t(__float_as_uint(d2[i])) << 32) | __float_as_uint(cur[i].w);
-    if (best[match[i]] != k) keep[i] = 0;
+    if (best[match_index_at(tgt_pts, match_pos[i])] != k) keep[i] = 0;
   }
 }
 
@@ -486,8 +488,8 @@ pclhip_status apply_correspondence_filters(pclhip_icp* icp, float max_d2, bool u
         const size_t nt = size_t(icp->target->n_orig);
         PCLHIP_CHECK_HIP(ctx, g.alloc(&best, nt * 8));
         PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(best, 0xFF, nt * 8, s));
-        hipLaunchKernelGGL(rej_o2o_min_kernel, grid, block, 0, s, icp->src_cur, icp->match, icp->match_d2, icp->keep, n,
-                           best);
+        hipLaunchKernelGGL(rej_o2o_min_kernel, grid, block, 0, s, icp->src_cur, icp->target->pts, icp->match_pos,
+                           icp->match_d2, icp->keep, n, best);
         if (icp_is_sharded(icp)) {  // target slabs: a target point of two halos may be matched on two ranks -- the global minimum wins
           // best[] is indexed by the GLOBAL target index: every rank must have built its index over the same whole cloud
           // plus its own subset list (pclhip.h, pclhip_icp_set_region) -- checked once per registration, not assumed
@@ -496,8 +498,8 @@ pclhip_status apply_correspondence_filters(pclhip_icp* icp, float max_d2, bool u
           const pclhip_status sm = allreduce_min_u64(icp, best, nt);
           if (sm != PCLHIP_OK) return sm;
         }
-        hipLaunchKernelGGL(rej_o2o_keep_kernel, grid, block, 0, s, icp->src_cur, icp->match, icp->match_d2, n, best,
-                           icp->keep);
+        hipLaunchKernelGGL(rej_o2o_keep_kernel, grid, block, 0, s, icp->src_cur, icp->target->pts, icp->match_pos,
+                           icp->match_d2, n, best, icp->keep);
         icp->fetch_order = 1;
         trimmed_in_chain = false;  // whatever an earlier Trimmed did to the order, this one re-orders the list
         break;

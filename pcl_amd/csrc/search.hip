@@ -856,7 +856,7 @@ __device__ __forceinline__ void icp_search_body(const IndexView& ix, float4* __r
                                                 const float4* __restrict__ src0, uint32_t ns, Mat34 T,
                                                 const IcpControl* __restrict__ ctl, const RegionBox& region, int order,
                                                 float bound, int flags, uint32_t* __restrict__ match_pos,
-                                                uint32_t* __restrict__ match, float* __restrict__ match_d2,
+                                                float* __restrict__ match_d2,
                                                 unsigned long long* gstats, IcpWaveLds* wl_s, Box* topbox_s,
                                                 const OG& og = OG()) {
   static_assert(!OWNED || Q == 1, "served-group lists are per 64-point group");
@@ -1065,28 +1065,34 @@ __device__ __forceinline__ void icp_search_body(const IndexView& ix, float4* __r
     }
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      NN1 pol;
-      pol.soa = ix.soa;
-      pol.key = KEY_NONE;
-      pol.pos = fast.bestpos[q];
-      if (fast.bestpos[q] != NO_INDEX) {  // winner's original index: already here when the seed won
-        const float w = (fast.bestpos[q] == seed_pos[q]) ? t0[q].w : ix.pts[fast.bestpos[q]].w;
-        pol.key = make_key(fast.best[q], __float_as_uint(w));
-      }
-      const bool redo[1] = {valid[q] && (fast.tie[q] || (fast.bestpos[q] == NO_INDEX && !use_max))};
+      // The match is its sorted position and its distance.  The ORIGINAL index only orders exact ties: it is gathered for
+      // the lanes that go through the exact policy and for nobody else (match_index_at serves whoever wants it later).
+      uint32_t pos = fast.bestpos[q];
+      float dist = fast.best[q];
+      bool has = pos != NO_INDEX;
+      const bool redo[1] = {valid[q] && (fast.tie[q] || (!has && !use_max))};
       if (__builtin_amdgcn_ballot_w64(redo[0]) != 0) {  // exact (distance, index) policy for tie lanes
-        NN1 ex = pol;
+        NN1 ex;
+        ex.soa = ix.soa;
+        ex.key = KEY_NONE;
+        ex.pos = pos;
+        if (redo[0] && has) {  // the winner's original index: already here when the seed won
+          const float w = (pos == seed_pos[q]) ? t0[q].w : ix.pts[pos].w;
+          ex.key = make_key(dist, __float_as_uint(w));
+        }
         const float ex_x[1] = {qx[q]}, ex_y[1] = {qy[q]}, ex_z[1] = {qz[q]};
         traverse<NN1, SPARSE>(ix, ex_x, ex_y, ex_z, redo, ex, wl_s[wave], topbox_s, ts);
-        if (redo[0]) pol = ex;
+        if (redo[0]) {
+          pos = ex.pos;
+          dist = key_dist(ex.key);
+          has = key_index(ex.key) != NO_INDEX;
+        }
       }
-      const uint32_t mid = key_index(pol.key);
-      const bool found = valid[q] && mid != NO_INDEX;
+      const bool found = valid[q] && has;
       if (in_range[q]) {
         const uint32_t i = gcur * GROUP + q * WAVE + lane;
-        match[i] = found ? mid : NO_INDEX;
-        match_pos[i] = found ? pol.pos : NO_INDEX;
-        match_d2[i] = found ? key_dist(pol.key) : __builtin_inff();
+        match_pos[i] = found ? pos : NO_INDEX;
+        match_d2[i] = found ? dist : __builtin_inff();
       }
     }
     if constexpr (OWNED) {
@@ -1116,7 +1122,7 @@ __device__ __forceinline__ void icp_cold_search_body(const IndexView& ix, float4
                                                      const float4* __restrict__ src0, uint32_t ns, Mat34 T,
                                                      const IcpControl* __restrict__ ctl, const RegionBox& region, int order,
                                                      float bound, int flags, float so_from,
-                                                     uint32_t* __restrict__ match_pos, uint32_t* __restrict__ match,
+                                                     uint32_t* __restrict__ match_pos,
                                                      float* __restrict__ match_d2, unsigned long long* gstats,
                                                      IcpWaveLds* wl_s, Box* topbox_s, const OG& og = OG()) {
   bool restart = false;
@@ -1143,7 +1149,7 @@ __device__ __forceinline__ void icp_cold_search_body(const IndexView& ix, float4
   PrevGroup prev;
   prev.init();
   // Runs of COLD_RUN consecutive -- spatially adjacent -- groups of the XCD's window, handed out IN ORDER by the XCD's
-  // counter (a wave's first run comes without asking; IndexView::sched_ctr, zeroed by PCLHIP_LAUNCH_FED): the waves of an
+  // counter (a wave's first run comes without asking; IndexView::sched_ctr, zero at every launch): the waves of an
   // XCD work on one front that marches over the kd order, and whoever is through first takes the next run.  Inside a run
   // a group borrows its predecessor's match as its seed; a run starts without one (one lane's exact neighbour).  Until
   // round 3's last day every wave owned ONE run of ~38 groups (fixed shares: the launch ended with its slowest wave, and
@@ -1205,27 +1211,31 @@ __device__ __forceinline__ void icp_cold_search_body(const IndexView& ix, float4
 #endif
     if (!done) traverse<NN1Min, true>(ix, qx, qy, qz, vv, fast, wl_s[wave], topbox_s, ts_fb, (flags & 2) ? hint : NO_INDEX, true);
     fast.resolve(ix, qx, qy, qz);
-    NN1 pol;
-    pol.soa = ix.soa;
-    pol.key = KEY_NONE;
-    pol.pos = fast.bestpos[0];
-    if (fast.bestpos[0] != NO_INDEX) pol.key = make_key(fast.best[0], __float_as_uint(ix.pts[fast.bestpos[0]].w));
+    uint32_t pos = fast.bestpos[0];  // (the original index: only where it orders a tie, see icp_search_body)
+    float dist = fast.best[0];
+    bool has = pos != NO_INDEX;
     {
-      const bool redo[1] = {valid && (fast.tie[0] || (fast.bestpos[0] == NO_INDEX && !use_max))};
+      const bool redo[1] = {valid && (fast.tie[0] || (!has && !use_max))};
       if (__builtin_amdgcn_ballot_w64(redo[0]) != 0) {  // exact (distance, index) policy for tie lanes
-        NN1 ex = pol;
+        NN1 ex;
+        ex.soa = ix.soa;
+        ex.key = KEY_NONE;
+        ex.pos = pos;
+        if (redo[0] && has) ex.key = make_key(dist, __float_as_uint(ix.pts[pos].w));
         traverse<NN1, true>(ix, qx, qy, qz, redo, ex, wl_s[wave], topbox_s, ts_fb);
-        if (redo[0]) pol = ex;
+        if (redo[0]) {
+          pos = ex.pos;
+          dist = key_dist(ex.key);
+          has = key_index(ex.key) != NO_INDEX;
+        }
       }
     }
-    const uint32_t mid = key_index(pol.key);
-    const bool found = valid && mid != NO_INDEX;
+    const bool found = valid && has;
     if (in_range) {
-      match[i] = found ? mid : NO_INDEX;
-      match_pos[i] = found ? pol.pos : NO_INDEX;
-      match_d2[i] = found ? key_dist(pol.key) : __builtin_inff();
+      match_pos[i] = found ? pos : NO_INDEX;
+      match_d2[i] = found ? dist : __builtin_inff();
     }
-    prev.record(p.x, p.y, p.z, found ? pol.pos : NO_INDEX);
+    prev.record(p.x, p.y, p.z, found ? pos : NO_INDEX);
 #if defined(PCLHIP_SO_PROFILE)
     ts.c[7] += uint32_t(clock64() - so_t0);
     if (!done) ++ts.c[4];
@@ -1249,13 +1259,12 @@ __global__ __launch_bounds__(BLOCK, MINW) void icp_search_kernel(IndexView ix, f
                                                                  Mat34 T, const IcpControl* __restrict__ ctl,
                                                                  RegionBox region, int order, float bound, int flags,
                                                                  uint32_t* __restrict__ match_pos,
-                                                                 uint32_t* __restrict__ match,
                                                                  float* __restrict__ match_d2,
                                                                  unsigned long long* gstats
                                                                  ) {
   __shared__ IcpWaveLds wl_s[WAVES_PER_BLOCK];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
-  icp_search_body<Q, SPARSE, false, NoOwnedGroups, DEEP>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos, match,
+  icp_search_body<Q, SPARSE, false, NoOwnedGroups, DEEP>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos,
                                                          match_d2, gstats, wl_s, topbox_s);
 }
 
@@ -1265,10 +1274,10 @@ __global__ __launch_bounds__(BLOCK, MINW) void icp_search_kernel(IndexView ix, f
 __global__ __launch_bounds__(BLOCK, PCLHIP_COLD_MINW) void icp_cold_search_kernel(
     IndexView ix, float4* __restrict__ cur, const float4* __restrict__ src0, uint32_t ns, Mat34 T,
     const IcpControl* __restrict__ ctl, RegionBox region, int order, float bound, int flags, float so_from,
-    uint32_t* __restrict__ match_pos, uint32_t* __restrict__ match, float* __restrict__ match_d2, unsigned long long* gstats) {
+    uint32_t* __restrict__ match_pos, float* __restrict__ match_d2, unsigned long long* gstats) {
   __shared__ IcpWaveLds wl_s[WAVES_PER_BLOCK];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
-  icp_cold_search_body(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos, match, match_d2, gstats,
+  icp_cold_search_body(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos, match_d2, gstats,
                        wl_s, topbox_s);
 }
 
@@ -1276,17 +1285,17 @@ template <bool DEEP>
 __global__ __launch_bounds__(BLOCK, PCLHIP_COLD_MINW) void icp_search_dual_kernel(
     IndexView ix, float4* __restrict__ cur, const float4* __restrict__ src0, uint32_t ns, Mat34 T,
     const IcpControl* __restrict__ ctl, RegionBox region, int order, float bound, int flags, float so_from,
-    uint32_t* __restrict__ match_pos, uint32_t* __restrict__ match, float* __restrict__ match_d2, unsigned long long* gstats
+    uint32_t* __restrict__ match_pos, float* __restrict__ match_d2, unsigned long long* gstats
     ) {
   __shared__ IcpWaveLds wl_s[WAVES_PER_BLOCK];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   if (ctl->restart != 0)
-    icp_cold_search_body(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos, match, match_d2, gstats,
+    icp_cold_search_body(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos, match_d2, gstats,
                          wl_s, topbox_s);
   else if ((flags & 4) != 0)
     return;  // SEARCH_RESTART_ONLY
   else
-    icp_search_body<1, true, false, NoOwnedGroups, DEEP>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos, match,
+    icp_search_body<1, true, false, NoOwnedGroups, DEEP>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos,
                                                          match_d2, gstats, wl_s, topbox_s);
 }
 
@@ -1295,15 +1304,15 @@ __global__ __launch_bounds__(BLOCK, PCLHIP_COLD_MINW) void icp_search_dual_kerne
 __global__ __launch_bounds__(BLOCK, PCLHIP_COLD_MINW) void icp_search_owned_kernel(
     IndexView ix, float4* __restrict__ cur, const float4* __restrict__ src0, uint32_t ns, Mat34 T,
     const IcpControl* __restrict__ ctl, RegionBox region, int order, float bound, int flags, float so_from, int standoff,
-    uint32_t* __restrict__ match_pos, uint32_t* __restrict__ match, float* __restrict__ match_d2, unsigned long long* gstats,
+    uint32_t* __restrict__ match_pos, float* __restrict__ match_d2, unsigned long long* gstats,
     OwnedGroups og) {
   __shared__ IcpWaveLds wl_s[WAVES_PER_BLOCK];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   if (standoff != 0 && ctl->restart != 0)
-    icp_cold_search_body<true, OwnedGroups>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos, match,
+    icp_cold_search_body<true, OwnedGroups>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, so_from, match_pos,
                                             match_d2, gstats, wl_s, topbox_s, og);
   else
-    icp_search_body<1, true, true, OwnedGroups>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos, match,
+    icp_search_body<1, true, true, OwnedGroups>(ix, cur, src0, ns, T, ctl, region, order, bound, flags, match_pos,
                                                 match_d2, gstats, wl_s, topbox_s, og);
 }
 
@@ -1356,7 +1365,6 @@ __global__ __launch_bounds__(BLOCK) void icp_own_flag_kernel(const IcpControl* _
                                                              const float4* __restrict__ gbox, RegionBox region,
                                                              uint32_t ngroups, uint32_t ns, uint32_t* __restrict__ stamp,
                                                              uint32_t* __restrict__ flags, uint32_t* __restrict__ block_count,
-                                                             uint32_t* __restrict__ match,
                                                              uint32_t* __restrict__ match_pos, float* __restrict__ match_d2) {
   if (ctl->stop != 0) return;
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1397,7 +1405,6 @@ __global__ __launch_bounds__(BLOCK) void icp_own_flag_kernel(const IcpControl* _
     flags[g] = own ? 1u : 0u;
     if (!own && (sv >> 31) == 0u) {
       for (uint32_t i = g * WAVE; i < ns && i < (g + 1u) * WAVE; ++i) {
-        match[i] = NO_INDEX;
         match_pos[i] = NO_INDEX;
         match_d2[i] = __builtin_inff();
       }
@@ -1865,7 +1872,11 @@ __global__ __launch_bounds__(FINALIZE_THREADS) void icp_finalize_kernel(const do
                                                                         double* __restrict__ sums,
                                                                         const IcpControl* __restrict__ ctl = nullptr,
                                                                         IcpControl* __restrict__ solve_ctl = nullptr,
-                                                                        IcpStepRecord* __restrict__ log = nullptr) {
+                                                                        IcpStepRecord* __restrict__ log = nullptr,
+                                                                        uint32_t* __restrict__ rearm_ctr = nullptr) {
+  // the search launch of this iteration is through with the context's group counters: zero again for the next fed kernel
+  // of the stream (PCLHIP_LAUNCH_REARM) -- also when the alignment has stopped, so the host need not know whether it has
+  sched_ctr_rearm(rearm_ctr);
   if (ctl != nullptr && ctl->stop != 0) return;
   __shared__ double red[32][NS + 1];
   __shared__ double total[NS];
@@ -2143,33 +2154,33 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
       // nothing of this file
     } else if (owned) {
       hipLaunchKernelGGL(icp_own_flag_kernel, dim3((ngroups + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, ctl, icp->own_state,
-                         icp->own_gbox, icp->region, ngroups, icp->n, icp->own_stamp, icp->own_flags, icp->own_prefix, icp->match,
+                         icp->own_gbox, icp->region, ngroups, icp->n, icp->own_stamp, icp->own_flags, icp->own_prefix,
                          icp->match_pos, icp->match_d2);
       hipLaunchKernelGGL(icp_own_list_kernel, dim3((ngroups + OWN_CHUNK - 1) / OWN_CHUNK), dim3(BLOCK), 0, s, ctl, icp->own_state,
                          icp->own_flags, icp->own_prefix, ngroups, icp->own_list, icp->own_tot);
       const int go = resident_blocks(ctx, icp_search_owned_kernel, ngroups);
       PCLHIP_LAUNCH_FED(ctx, icp_search_owned_kernel, dim3(go), dim3(BLOCK), 0, s, v, icp->src_cur, icp->src_sorted0, icp->n, M,
-                         ctl, icp->region, order, bound, kflags, so_from, standoff ? 1 : 0, icp->match_pos, icp->match,
+                         ctl, icp->region, order, bound, kflags, so_from, standoff ? 1 : 0, icp->match_pos,
                          icp->match_d2, ctx->stats, og);
     } else if (standoff && device_loop) {
       const int gd = resident_blocks(ctx, icp_search_dual_kernel<false>, ngroups);
       if (deep_for(gd, ngroups)) {
         PCLHIP_LAUNCH_FED(ctx, icp_search_dual_kernel<true>, dim3(gd), dim3(BLOCK), 0, s, v, icp->src_cur, icp->src_sorted0, icp->n, M,
-                           ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match, icp->match_d2, ctx->stats);
+                           ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match_d2, ctx->stats);
       } else {
         PCLHIP_LAUNCH_FED(ctx, icp_search_dual_kernel<false>, dim3(gd), dim3(BLOCK), 0, s, v, icp->src_cur, icp->src_sorted0, icp->n, M,
-                           ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match, icp->match_d2, ctx->stats);
+                           ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match_d2, ctx->stats);
       }
     } else if (cold) {
       const int gc = resident_blocks(ctx, icp_cold_search_kernel, ngroups);
       PCLHIP_LAUNCH_FED(ctx, icp_cold_search_kernel, dim3(gc), dim3(BLOCK), 0, s, v, icp->src_cur, icp->src_sorted0, icp->n, M,
-                         ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match, icp->match_d2,
+                         ctl, icp->region, order, bound, kflags, so_from, icp->match_pos, icp->match_d2,
                          ctx->stats);
     } else {
       const int gk = resident_blocks(ctx, ks, ngroups);
       if (deep_for(gk, ngroups)) ks = icp_search_kernel<4, 1, true, true>;
       PCLHIP_LAUNCH_FED(ctx, ks, dim3(gk), dim3(BLOCK), 0, s, v, icp->src_cur, icp->src_sorted0,
-                         icp->n, M, ctl, icp->region, order, bound, kflags, icp->match_pos, icp->match, icp->match_d2, ctx->stats);
+                         icp->n, M, ctl, icp->region, order, bound, kflags, icp->match_pos, icp->match_d2, ctx->stats);
     }
     if (lane_now) {
       const pclhip_status lst = launch_lane_search(icp, M.m, ctl, order, bound, use_max);
@@ -2214,8 +2225,11 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
     // (Folding this reduction into the accumulate kernel -- last block done -- was tried: the 2048 device-scope
     // atomics on one counter cost ~100 us across the 8 XCDs, five times this 20 us launch.)
     solved = device_loop && !icp_is_sharded(icp);  // no record to exchange: the reduction launch closes the iteration
-    hipLaunchKernelGGL(icp_finalize_kernel, dim3(1), dim3(FINALIZE_THREADS), 0, s, icp->partials, ga, icp->sums_dev, ctl,
-                       solved ? icp->ctl : static_cast<IcpControl*>(nullptr), icp->steps);
+    // ... and re-arms the group counters behind the search launch(es) of this iteration, host- or device-driven, whichever
+    // search kernel ran (the served-group lists and the reciprocal search included; the per-lane kernels take no tickets).
+    // Under sharding icp_solve_kernel follows, but nothing between the two is fed, so the re-arm stays here.
+    PCLHIP_LAUNCH_REARM(ctx, icp_finalize_kernel, dim3(1), dim3(FINALIZE_THREADS), 0, s, icp->partials, ga, icp->sums_dev, ctl,
+                        solved ? icp->ctl : static_cast<IcpControl*>(nullptr), icp->steps, ctx->sched_ctr);
   } else {
     if (device_loop) {
       (void)hipEventRecord(ev[0], s);
@@ -2270,15 +2284,14 @@ pclhip_status launch_fitness_score(pclhip_icp* icp, const float T[16], double ma
   const Mat34 M = mat34_of(T);
   const uint32_t n = icp->n;
   const int gr = ctx->num_cus * 4;
-  // scratch: transformed copy of the source, seed/match positions, match ids, distances, partials
-  const size_t o_pos = size_t(n) * sizeof(float4), o_id = o_pos + size_t(n) * 4, o_d2 = o_id + size_t(n) * 4;
+  // scratch: transformed copy of the source, seed/match positions, distances, partials
+  const size_t o_pos = size_t(n) * sizeof(float4), o_d2 = o_pos + size_t(n) * 4;
   const size_t o_part = (o_d2 + size_t(n) * 4 + 15) & ~size_t(15);
   pclhip_status st = ensure_scratch(ctx, o_part + size_t(gr) * 2 * sizeof(double));
   if (st != PCLHIP_OK) return st;
   char* base = static_cast<char*>(ctx->scratch);
   float4* cur = reinterpret_cast<float4*>(base);
   uint32_t* pos = reinterpret_cast<uint32_t*>(base + o_pos);
-  uint32_t* id = reinterpret_cast<uint32_t*>(base + o_id);
   float* d2 = reinterpret_cast<float*>(base + o_d2);
   double* part = reinterpret_cast<double*>(base + o_part);
   PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(cur, icp->src_sorted0, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, s));
@@ -2292,7 +2305,7 @@ pclhip_status launch_fitness_score(pclhip_icp* icp, const float T[16], double ma
   // target sharding: this rank scores the source points whose position under T lies in its region (every point has
   // exactly one owner), against its slab + halo index; the (sum, count) pairs are summed over the ranks below
   PCLHIP_LAUNCH_FED(ctx, (icp_search_kernel<4, 1, true>), dim3(gs), dim3(BLOCK), 0, s, v, cur, static_cast<const float4*>(cur), n,
-                     M, static_cast<const IcpControl*>(nullptr), icp->region, 1, __builtin_inff(), fit_flags, pos, id, d2,
+                     M, static_cast<const IcpControl*>(nullptr), icp->region, 1, __builtin_inff(), fit_flags, pos, d2,
                      ctx->stats);
   hipLaunchKernelGGL(fitness_partial_kernel, dim3(gr), dim3(BLOCK), 0, s, d2, n, max_range, part);
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
@@ -2354,6 +2367,7 @@ int icp_grid_blocks(pclhip_ctx* ctx, uint32_t ns) {
   const uint32_t ngroups = (ns + WAVE - 1) / WAVE;
   int g = resident_blocks(ctx, icp_search_kernel<4, 1, true>, ngroups);
   if (ctx->num_cus * 8 > g) g = ctx->num_cus * 8;  // the streaming accumulate kernel
+  if (g < 64) g = 64;  // ... of which launch_icp_iterate never runs fewer than 64 (matters below 8 CUs: rows of icp->partials)
   return g;
 }
 

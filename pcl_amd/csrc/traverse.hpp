@@ -1415,7 +1415,7 @@ struct GroupSchedule {
 // points, each between half and twice the mean: the normals kernel ran 1.86 ms where its waves were busy for 1.5.  A wave
 // strides over the first HALF of its XCD's groups like GroupSchedule (equal shares, no traffic), then takes the remaining
 // ones one at a time from the XCD's counter: whoever is through first takes more, and the waves of an XCD still work on
-// adjacent groups.  The counters (IndexView::sched_ctr; zeroed in stream order by PCLHIP_LAUNCH_FED) are asked one group
+// adjacent groups.  The counters (IndexView::sched_ctr; zero at every launch: PCLHIP_LAUNCH_FED) are asked one group
 // AHEAD of use -- ahead() at the top of a group, advance() at its bottom -- so the atomic's round trip is off the
 // critical path.  Measured at 10M points (static share 7/8, 3/4, 1/2, one round): normals 1.76 / 1.67 / 1.49 / 1.50 ms,
 // ms per ICP step 1.28 / 1.244 / 1.243 / 1.26 (1.326 with fixed shares).
