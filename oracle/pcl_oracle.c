@@ -1151,8 +1151,8 @@ static void compute_roots2(float b, float c, float* roots) {
   roots[1] = 0.5f * (b - sd);
 }
 
-/* eigen.hpp:68-128; m is row-major symmetric 3x3 */
-static void compute_roots(const float* m, float* roots) {
+/* eigen.hpp:68-128; m is row-major symmetric 3x3.  `path` (optional): ORC_ROOTS_* of the way taken */
+static void compute_roots(const float* m, float* roots, int32_t* path) {
 #define M(i, j) m[(i)*3 + (j)]
   float c0 = M(0, 0) * M(1, 1) * M(2, 2) + 2.0f * M(0, 1) * M(0, 2) * M(1, 2) -
              M(0, 0) * M(1, 2) * M(1, 2) - M(1, 1) * M(0, 2) * M(0, 2) - M(2, 2) * M(0, 1) * M(0, 1);
@@ -1161,8 +1161,10 @@ static void compute_roots(const float* m, float* roots) {
   float c2 = M(0, 0) + M(1, 1) + M(2, 2);
 #undef M
   if (fabsf(c0) < FLT_EPSILON) {
+    if (path) *path = ORC_ROOTS_C0;
     compute_roots2(c2, c1, roots);
   } else {
+    if (path) *path = ORC_ROOTS_TRIG;
     const float s_inv3 = (float)(1.0 / 3.0);
     const float s_sqrt3 = sqrtf(3.0f);
     float c2_over_3 = c2 * s_inv3;
@@ -1194,7 +1196,10 @@ static void compute_roots(const float* m, float* roots) {
         roots[1] = t;
       }
     }
-    if (roots[0] <= 0) compute_roots2(c2, c1, roots);
+    if (roots[0] <= 0) {
+      if (path) *path = ORC_ROOTS_TRIG_FALLBACK;
+      compute_roots2(c2, c1, roots);
+    }
   }
 }
 
@@ -1223,10 +1228,11 @@ static void largest_eigvec(const float* sm, float* v) {
 }
 
 /* Eigen unitOrthogonal for 3-vectors (used only in the degenerate branch eigen.hpp:316-318) */
-static void unit_orthogonal(const float* s, float* o) {
+static void unit_orthogonal(const float* s, float* o, int32_t* arm) {
   const float prec = 1e-5f; /* NumTraits<float>::dummy_precision() */
   int x_small = fabsf(s[0]) <= prec * fabsf(s[2]);
   int y_small = fabsf(s[1]) <= prec * fabsf(s[2]);
+  if (arm) *arm = (!x_small || !y_small) ? 1 : 2;
   if (!x_small || !y_small) {
     float inv = 1.0f / sqrtf(s[0] * s[0] + s[1] * s[1]);
     o[0] = -s[1] * inv;
@@ -1240,17 +1246,24 @@ static void unit_orthogonal(const float* s, float* o) {
   }
 }
 
-/* eigen.hpp:295-325 */
-static void eigen33(const float* mat, float* eigenvalue, float* vec) {
+/* eigen.hpp:295-325.  `rec` (optional) receives the path taken; the arithmetic is the same with and without it */
+static void eigen33(const float* mat, float* eigenvalue, float* vec, orc_plane_path* rec) {
   float scale = 0.0f;
   for (int i = 0; i < 9; ++i)
     if (fabsf(mat[i]) > scale) scale = fabsf(mat[i]);
+  if (rec) rec->scale_small = scale <= FLT_MIN;
   if (scale <= FLT_MIN) scale = 1.0f;
   float sm[9];
   for (int i = 0; i < 9; ++i) sm[i] = mat[i] / scale;
   float ev[3];
-  compute_roots(sm, ev);
+  compute_roots(sm, ev, rec ? &rec->roots_path : NULL);
   *eigenvalue = ev[0] * scale;
+  if (rec) {
+    rec->gap10 = ev[1] - ev[0];
+    rec->gap20 = ev[2] - ev[0];
+    rec->eigvec_branch = (ev[1] - ev[0]) > FLT_EPSILON ? 1 : (ev[2] - ev[0]) > FLT_EPSILON ? 2 : 3;
+    rec->orthogonal_arm = 0;
+  }
   if ((ev[1] - ev[0]) > FLT_EPSILON) {
     sm[0] -= ev[0];
     sm[4] -= ev[0];
@@ -1262,7 +1275,7 @@ static void eigen33(const float* mat, float* eigenvalue, float* vec) {
     sm[8] -= ev[2];
     float tmp[3];
     largest_eigvec(sm, tmp);
-    unit_orthogonal(tmp, vec);
+    unit_orthogonal(tmp, vec, rec ? &rec->orthogonal_arm : NULL);
   } else {
     vec[0] = 1.0f;
     vec[1] = 0.0f;
@@ -1270,18 +1283,47 @@ static void eigen33(const float* mat, float* eigenvalue, float* vec) {
   }
 }
 
-void orc_solve_plane_parameters(const float* cov, float* nx, float* ny, float* nz,
-                                float* curvature) {
+void orc_solve_plane_parameters_path(const float* cov, float* nx, float* ny, float* nz, float* curvature,
+                                     orc_plane_path* rec) {
   float ev, v[3];
-  eigen33(cov, &ev, v);
+  eigen33(cov, &ev, v, rec);
   *nx = v[0];
   *ny = v[1];
   *nz = v[2];
   float eig_sum = cov[0] + cov[4] + cov[8]; /* feature.hpp:84 */
+  if (rec) rec->eig_sum_zero = !(eig_sum != 0);
   if (eig_sum != 0)
     *curvature = fabsf(ev / eig_sum);
   else
     *curvature = 0;
+}
+
+void orc_solve_plane_parameters(const float* cov, float* nx, float* ny, float* nz,
+                                float* curvature) {
+  orc_solve_plane_parameters_path(cov, nx, ny, nz, curvature, NULL);
+}
+
+/* The plane fits of `nrows` neighbour lists (row j: idx[j * width ...], -1 = no entry, in the order the sums take them):
+ * computePointNormal without the viewpoint flip, and the path of each fit.  Fewer than 3 entries: NaN row, roots_path
+ * ORC_ROOTS_NONE. */
+void orc_plane_fit_lists(const float* cloud, int cs, const int32_t* idx, int width, int64_t nrows, float* out,
+                         orc_plane_path* recs) {
+  int32_t* list = (int32_t*)malloc((size_t)(width > 0 ? width : 1) * sizeof(int32_t));
+  for (int64_t j = 0; j < nrows; ++j) {
+    int n = 0;
+    for (int c = 0; c < width; ++c)
+      if (idx[j * width + c] >= 0) list[n++] = idx[j * width + c];
+    float cov[9], cen[4];
+    float* o = out + 4 * j;
+    memset(&recs[j], 0, sizeof(orc_plane_path));
+    recs[j].roots_path = ORC_ROOTS_NONE;
+    if (n < 3 || orc_mean_and_covariance(cloud, cs, list, n, cov, cen) == 0) {
+      o[0] = o[1] = o[2] = o[3] = NAN;
+      continue;
+    }
+    orc_solve_plane_parameters_path(cov, &o[0], &o[1], &o[2], &o[3], &recs[j]);
+  }
+  free(list);
 }
 
 /* computeFeature loops over indices_ (features/include/pcl/features/impl/normal_3d.hpp:59,74): with

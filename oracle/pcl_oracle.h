@@ -175,6 +175,23 @@ unsigned orc_mean_and_covariance(const float* cloud, int cs, const int32_t* indi
  * (common/include/pcl/common/impl/eigen.hpp:295-325, computeRoots :68-128). */
 void orc_solve_plane_parameters(const float* cov9, float* nx, float* ny, float* nz,
                                 float* curvature);
+/* Which way one plane fit went through eigen33 / computeRoots (tests pick their rows by it). */
+enum { ORC_ROOTS_NONE = -1, ORC_ROOTS_C0 = 0, ORC_ROOTS_TRIG = 1, ORC_ROOTS_TRIG_FALLBACK = 2 };
+typedef struct {
+  int32_t roots_path;     /* ORC_ROOTS_C0: |c0| < FLT_EPSILON -> computeRoots2; _TRIG; _TRIG_FALLBACK: trig, then
+                             roots[0] <= 0 -> computeRoots2 */
+  int32_t eigvec_branch;  /* 1: ev[1]-ev[0] > eps; 2: ev[2]-ev[0] > eps (unitOrthogonal); 3: the constant (1,0,0) */
+  int32_t orthogonal_arm; /* 0: unitOrthogonal not reached; 1: its x-y arm; 2: its y-z arm */
+  int32_t scale_small;    /* scale <= FLT_MIN (the matrix is then not scaled) */
+  int32_t eig_sum_zero;   /* trace of the covariance == 0: curvature 0 */
+  float gap10, gap20;     /* ev[1]-ev[0], ev[2]-ev[0] of the scaled matrix */
+} orc_plane_path;
+/* The same function with the record filled in (rec may be NULL: orc_solve_plane_parameters is this with NULL). */
+void orc_solve_plane_parameters_path(const float* cov9, float* nx, float* ny, float* nz, float* curvature,
+                                     orc_plane_path* rec);
+/* Plane fits (no viewpoint flip) and their paths for nrows neighbour lists of `width` slots each, -1 = empty slot. */
+void orc_plane_fit_lists(const float* cloud, int cs, const int32_t* idx, int width, int64_t nrows, float* out,
+                         orc_plane_path* recs);
 /* NormalEstimation::computeFeature with k-NN (features/include/pcl/features/impl/normal_3d.hpp
  * :48-95) over the whole cloud with surface == input; flipNormalTowardsViewpoint
  * (normal_3d.h:169-188).  out = n x 4 floats (nx, ny, nz, curvature).  out_knn (optional) n*k

@@ -47,6 +47,18 @@ class IcpResult(C.Structure):
                 ("seconds_search", C.c_double), ("seconds_total", C.c_double)]
 
 
+class PlanePath(C.Structure):
+    """orc_plane_path: which way one plane fit went through eigen33 / computeRoots"""
+    _fields_ = [("roots_path", C.c_int32), ("eigvec_branch", C.c_int32), ("orthogonal_arm", C.c_int32),
+                ("scale_small", C.c_int32), ("eig_sum_zero", C.c_int32), ("gap10", C.c_float), ("gap20", C.c_float)]
+
+
+ROOTS_NONE, ROOTS_C0, ROOTS_TRIG, ROOTS_TRIG_FALLBACK = -1, 0, 1, 2
+PLANE_PATH_DTYPE = np.dtype([("roots_path", np.int32), ("eigvec_branch", np.int32), ("orthogonal_arm", np.int32),
+                             ("scale_small", np.int32), ("eig_sum_zero", np.int32), ("gap10", np.float32),
+                             ("gap20", np.float32)])
+assert PLANE_PATH_DTYPE.itemsize == C.sizeof(PlanePath)
+
 _lib = None
 
 
@@ -103,6 +115,8 @@ def lib():
         L.orc_mean_and_covariance.restype = C.c_uint
         L.orc_mean_and_covariance.argtypes = [fp, C.c_int, ip, C.c_int, fp, fp]
         L.orc_solve_plane_parameters.argtypes = [fp, fp, fp, fp, fp]
+        L.orc_solve_plane_parameters_path.argtypes = [fp, fp, fp, fp, fp, C.POINTER(PlanePath)]
+        L.orc_plane_fit_lists.argtypes = [fp, C.c_int, ip, C.c_int, C.c_int64, fp, vp]
         L.orc_normals_knn.restype = C.c_int64
         L.orc_normals_knn.argtypes = [vp, fp, C.c_int64, C.c_int, C.c_int, fp, fp, ip, C.c_int]
         L.orc_normals_knn_indices.restype = C.c_int64
@@ -394,6 +408,28 @@ def solve_plane_parameters(cov):
     out = [C.c_float() for _ in range(4)]
     lib().orc_solve_plane_parameters(_f(cov), *[C.byref(o) for o in out])
     return tuple(o.value for o in out)
+
+
+def solve_plane_parameters_path(cov):
+    """solve_plane_parameters and the path it took: ((nx, ny, nz, curvature), dict of the PlanePath fields)"""
+    cov = np.ascontiguousarray(cov, np.float32).reshape(9)
+    out = [C.c_float() for _ in range(4)]
+    rec = PlanePath()
+    lib().orc_solve_plane_parameters_path(_f(cov), *[C.byref(o) for o in out], C.byref(rec))
+    return tuple(o.value for o in out), {n: getattr(rec, n) for n, _ in PlanePath._fields_}
+
+
+def plane_fit_lists(cloud, lists):
+    """The plane fit of every row of `lists` (int32 (rows, width) indices into cloud, -1 = empty slot, taken in the row's
+    order) without the viewpoint flip -> ((rows, 4) float32, structured array PLANE_PATH_DTYPE).  Fewer than 3 entries:
+    NaN row, roots_path ROOTS_NONE."""
+    cloud, n, cs = _cloud(cloud)
+    lists = np.ascontiguousarray(lists, np.int32)
+    assert lists.ndim == 2 and (lists < n).all()
+    out = np.empty((len(lists), 4), np.float32)
+    recs = np.zeros(len(lists), PLANE_PATH_DTYPE)
+    lib().orc_plane_fit_lists(_f(cloud), cs, _i(lists), lists.shape[1], len(lists), _f(out), C.c_void_p(recs.ctypes.data))
+    return out, recs
 
 
 def voxelgrid(cloud, leaf, min_points_per_voxel=0, limits=None, field=2, negative=False):
