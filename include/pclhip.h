@@ -295,6 +295,34 @@ PCLHIP_API pclhip_status pclhip_fpfh(pclhip_index* index, const int32_t* indices
                                      void* out, size_t out_stride_bytes, float* out_spfh, uint64_t* out_nan_count);
 /* GPU time (ms) of the SPFH kernel and of the weighting kernel of the last pclhip_fpfh on this index. */
 PCLHIP_API void pclhip_index_last_fpfh_ms(const pclhip_index* index, double* spfh_ms, double* weight_ms);
+/* pcl::EuclideanClusterExtraction<PointT>::extract (segmentation/.../impl/extract_clusters.hpp:124-253): the clusters are
+ * the connected components of the graph over the index's points with an edge wherever float d2 < float(r * r),
+ * r = double(float(tolerance)) -- the relation of pclhip_radius_search.  The index defines the set of points: built with
+ * `indices`, only those are clustered (the reference's (cloud, indices) overload with a tree over the same set) and the
+ * ids are original ones; a scaled index clusters in its rescaled space.  A component is kept when min_size <= size <=
+ * max_size; the kept clusters are ordered by size descending, ties by their smallest original index ascending (the
+ * reference's std::sort leaves ties unspecified); every cluster's indices ascend.
+ *   out_labels   (host or device, n_orig entries, optional) rank of the record's cluster in output order; -1 for a record
+ *                in no returned cluster (non-finite, not selected, or in a cluster outside the size range)
+ *   out_offsets  (HOST, optional) n_clusters + 1 entries: cluster c is out_indices[out_offsets[c] .. out_offsets[c + 1])
+ *   out_indices  (host or device, optional) n_clustered entries
+ * The counts are always written; a capacity that is too small gives PCLHIP_ERR_OVERFLOW after the counts and the labels
+ * are written (n_orig indices and n_orig + 1 offsets always suffice).  tolerance < 0 or not finite is PCLHIP_ERR_INVALID;
+ * tolerance == 0, or a positive tolerance whose float square is 0, is a valid call in which no point has a neighbour and
+ * every finite point is its own cluster (:177-181).  min_size > max_size or an empty index give zero clusters.
+ * The result does not depend on the order the device worked in: two calls give the same bytes.
+ * Deviation: a non-finite record belongs to no cluster (the reference asserts on such a query and, in a release build,
+ * makes it a singleton).
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_cluster_stats that of its union-find
+ * kernels. */
+PCLHIP_API pclhip_status pclhip_euclidean_clusters(pclhip_index* index, double tolerance, uint32_t min_size,
+                                                   uint32_t max_size, int32_t* out_labels, uint64_t* out_offsets,
+                                                   uint64_t offsets_capacity, int32_t* out_indices,
+                                                   uint64_t indices_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+/* GPU time (ms) of the hook and of the flatten kernel of the last pclhip_euclidean_clusters on this index, and the number
+ * of unions its hook kernel attempted (a hit under another root; depends on the order the device worked in). */
+PCLHIP_API void pclhip_index_last_cluster_stats(const pclhip_index* index, double* hook_ms, double* flatten_ms,
+                                                uint64_t* unions);
 /* GPU time (ms) of the last pclhip_knn / pclhip_normals traversal kernel on this index. */
 PCLHIP_API double pclhip_index_last_kernel_ms(const pclhip_index* index);
 /* Supply target normals computed elsewhere (e.g. a pcl::PointNormal target: normals = points + 16,

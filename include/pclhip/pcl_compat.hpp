@@ -45,6 +45,7 @@
 namespace pclhip {
 
 using index_t = std::int32_t;           // common/include/pcl/types.h:110-133
+using uindex_t = std::uint32_t;
 using Indices = std::vector<index_t>;
 using IndicesPtr = std::shared_ptr<Indices>;
 using IndicesConstPtr = std::shared_ptr<const Indices>;
@@ -1893,6 +1894,76 @@ class RadiusOutlierRemoval : public OutlierRemovalBase<PointT> {
   }
   double radius_ = 0.0;
   int min_pts_ = 1;
+};
+
+// ---- segmentation: pcl::PointIndices (common/include/pcl/PointIndices.h; `indices` only) and
+// pcl::EuclideanClusterExtraction<PointT> (segmentation/include/pcl/segmentation/extract_clusters.h:330-435,
+// impl/extract_clusters.hpp:223-253) over pclhip_euclidean_clusters.  Largest cluster first; clusters of equal size by their
+// smallest index (the reference leaves that order to an unstable sort).
+struct PointIndices {
+  using Ptr = std::shared_ptr<PointIndices>;
+  using ConstPtr = std::shared_ptr<const PointIndices>;
+  Indices indices;
+};
+
+template <typename PointT>
+class EuclideanClusterExtraction : public PCLBase<PointT> {
+ public:
+  using KdTree = search::Search<PointT>;
+  using KdTreePtr = typename KdTree::Ptr;
+  EuclideanClusterExtraction() : EuclideanClusterExtraction(Context::defaultContext()) {}
+  explicit EuclideanClusterExtraction(Context::Ptr ctx) : ctx_(std::move(ctx)) {}
+  // a pclhip::search::KdTree is rebuilt over (input, indices) and used, as the reference does with its tree (:242); any
+  // other Search is ignored and the extraction builds its own index
+  void setSearchMethod(const KdTreePtr& tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setClusterTolerance(double tolerance) { cluster_tolerance_ = tolerance; }
+  double getClusterTolerance() const { return cluster_tolerance_; }
+  void setMinClusterSize(uindex_t n) { min_pts_per_cluster_ = n; }
+  uindex_t getMinClusterSize() const { return min_pts_per_cluster_; }
+  void setMaxClusterSize(uindex_t n) { max_pts_per_cluster_ = n; }
+  uindex_t getMaxClusterSize() const { return max_pts_per_cluster_; }
+  const std::string& getLastError() const { return error_; }
+  // per record of the input: the rank of its cluster in the last extract(), -1 for a record in no returned cluster
+  const std::vector<std::int32_t>& getLabels() const { return labels_; }
+
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    labels_.clear();
+    error_.clear();
+    if (!this->input_ || this->input_->empty() || !ctx_ || !ctx_->ok()) return;
+    const bool subset = this->indices_ && !this->fake_indices_;
+    if (subset && this->indices_->empty()) return;  // :226-232
+    auto tree = std::dynamic_pointer_cast<search::KdTree<PointT>>(tree_);
+    if (!tree) tree = std::make_shared<search::KdTree<PointT>>(ctx_);
+    if (!tree->setInputCloud(this->input_, subset ? IndicesConstPtr(this->indices_) : IndicesConstPtr())) {
+      error_ = pclhip_last_error(ctx_->get());
+      return;
+    }
+    const std::size_t n = this->input_->size();
+    std::vector<std::uint64_t> offsets(n + 1, 0);
+    Indices flat(n);
+    labels_.assign(n, -1);
+    std::uint64_t k = 0, nc = 0;
+    if (pclhip_euclidean_clusters(tree->handle(), cluster_tolerance_, min_pts_per_cluster_, max_pts_per_cluster_,
+                                  labels_.data(), offsets.data(), n + 1, flat.data(), n, &k, &nc) != PCLHIP_OK) {
+      error_ = pclhip_last_error(tree->context()->get());
+      labels_.clear();
+      return;
+    }
+    clusters.resize(std::size_t(k));
+    for (std::size_t c = 0; c < std::size_t(k); ++c)
+      clusters[c].indices.assign(flat.begin() + long(offsets[c]), flat.begin() + long(offsets[c + 1]));
+  }
+
+ private:
+  Context::Ptr ctx_;
+  KdTreePtr tree_;
+  double cluster_tolerance_ = 0.0;  // extract_clusters.h:425-431: the reference's defaults
+  uindex_t min_pts_per_cluster_ = 1;
+  uindex_t max_pts_per_cluster_ = std::numeric_limits<uindex_t>::max();
+  std::vector<std::int32_t> labels_;
+  std::string error_;
 };
 
 }  // namespace pclhip

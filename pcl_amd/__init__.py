@@ -6,7 +6,7 @@ from . import synth  # noqa: F401
 from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SYMMETRIC, PclHipError, PclHipUnavailable)  # noqa: F401
 from .api import (Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
-                  CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, FPFHEstimation, GeneralizedIterativeClosestPoint,
+                  CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
                   RadiusOutlierRemoval, SampleConsensusPrerejective,

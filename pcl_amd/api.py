@@ -7,6 +7,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::NormalEstimation                                features/include/pcl/features/normal_3d.h:243-420
   pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
+  pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
 Clouds are (n, c>=3) float32 arrays: numpy (host) or torch CUDA tensors (device-resident; only the
 pointer crosses the boundary).  All compute happens in libpclhip.so; there is no CPU fallback.
 """
@@ -2059,6 +2060,112 @@ class FPFHEstimation:
     def computeBoth(self):
         """-> ((m, 33) FPFH, (n, 33) SPFH) of one call."""
         return self._run(True, True)
+
+
+class EuclideanClusterExtraction:
+    """pcl::EuclideanClusterExtraction<PointT> (segmentation/include/pcl/segmentation/extract_clusters.h:330-435,
+    impl/extract_clusters.hpp:124-253) over pclhip_euclidean_clusters.  The input is an (n, c >= 3) float32 cloud, numpy or
+    a torch CUDA tensor; the clusters come back in the same kind of array, largest first, ties by smallest index."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self._tree = None
+        self._cloud = None
+        self._indices = None
+        self._tolerance = 0.0                 # extract_clusters.h:360-435: the reference's defaults
+        self._min = 1
+        self._max = 0xFFFFFFFF
+        self._labels = None
+        self._ms = 0.0
+
+    def getClassName(self):
+        return "EuclideanClusterExtraction"
+
+    def setInputCloud(self, cloud):
+        self._cloud = cloud
+
+    def getInputCloud(self):
+        return self._cloud
+
+    def setIndices(self, indices):
+        """PCLBase::setIndices: only these records are clustered (None: every record)."""
+        self._indices = indices
+
+    def getIndices(self):
+        return self._indices
+
+    def setSearchMethod(self, tree):
+        self._tree = tree
+
+    def getSearchMethod(self):
+        return self._tree
+
+    def setClusterTolerance(self, tolerance):
+        self._tolerance = float(tolerance)
+
+    def getClusterTolerance(self):
+        return self._tolerance
+
+    def setMinClusterSize(self, n):
+        self._min = int(n)
+
+    def getMinClusterSize(self):
+        return self._min
+
+    def setMaxClusterSize(self, n):
+        self._max = int(n)
+
+    def getMaxClusterSize(self):
+        return self._max
+
+    def lastKernelMs(self):
+        """GPU time of the last extract() (all of its kernels)."""
+        return self._ms
+
+    def lastStats(self):
+        """dict(hook_ms, flatten_ms, unions) of the last extract(): the two union-find kernels and the unions attempted."""
+        a, b, u = C.c_double(0.0), C.c_double(0.0), C.c_uint64(0)
+        self.lib.pclhip_index_last_cluster_stats(self._tree.h, C.byref(a), C.byref(b), C.byref(u))
+        return dict(hook_ms=a.value, flatten_ms=b.value, unions=int(u.value))
+
+    def extractCSR(self):
+        """-> (offsets uint64 [k + 1] (numpy), indices int32 [n_clustered], labels int32 [n]) of one call; indices and
+        labels are torch device tensors for a torch cloud."""
+        assert self._cloud is not None, "setInputCloud first"
+        if self._tree is None:
+            self._tree = KdTree(self.ctx)
+        key = (id(self._cloud), None if self._indices is None else id(self._indices))
+        if self._tree.h is None or self._tree._cloud_id != key:  # a tree built for another cloud or index set
+            self._tree.setInputCloud(self._cloud, self._indices)
+        n = self._tree.n_cloud
+        offsets = np.zeros(n + 1, np.uint64)
+        if _is_torch(self._cloud):
+            import torch
+            labels = torch.empty(n, dtype=torch.int32, device=self._cloud.device)
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=self._cloud.device)
+            lp, ip = C.c_void_p(labels.data_ptr()), C.c_void_p(idx.data_ptr())
+        else:
+            labels = np.empty(n, np.int32)
+            idx = np.empty(max(n, 1), np.int32)
+            lp, ip = C.c_void_p(labels.ctypes.data), C.c_void_p(idx.ctypes.data)
+        k, nc = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.pclhip_euclidean_clusters(self._tree.h, self._tolerance, max(self._min, 0), min(self._max, 0xFFFFFFFF),
+                                                 lp, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n + 1, ip, n,
+                                                 C.byref(k), C.byref(nc)), self.ctx.h)
+        self._ms = float(self.lib.pclhip_index_last_kernel_ms(self._tree.h))
+        self._labels = labels
+        return offsets[:k.value + 1], idx[:nc.value], labels
+
+    def extract(self):
+        """extract(std::vector<PointIndices>&): a list of ascending int32 index arrays."""
+        offsets, idx, _ = self.extractCSR()
+        off = offsets.astype(np.int64).tolist()
+        return [idx[off[c]:off[c + 1]] for c in range(len(off) - 1)]
+
+    def labels(self):
+        """Per record of the cloud: the rank of its cluster in the last extract(), -1 for a record in no returned cluster."""
+        return self._labels
 
 
 def featureKSearch(ctx, target_rows, query_rows, k):

@@ -1387,6 +1387,32 @@ void pclhip_index_last_fpfh_ms(const pclhip_index* ix, double* spfh_ms, double* 
   if (weight_ms) *weight_ms = ix ? ix->fpfh_pass_ms[1] : 0.0;
 }
 
+// ---- EuclideanClusterExtraction (cluster.hpp) ------------------------------------------------------
+pclhip_status pclhip_euclidean_clusters(pclhip_index* ix, double tolerance, uint32_t min_size, uint32_t max_size,
+                                        int32_t* out_labels, uint64_t* out_offsets, uint64_t offsets_capacity,
+                                        int32_t* out_indices, uint64_t indices_capacity, uint64_t* n_clusters,
+                                        uint64_t* n_clustered) {
+  if (!ix || !n_clusters || !n_clustered) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_clusters = 0;
+  *n_clustered = 0;
+  PCLHIP_REQUIRE(ctx, std::isfinite(tolerance) && tolerance >= 0.0, "the cluster tolerance must be finite and >= 0");
+  PCLHIP_REQUIRE(ctx, out_offsets == nullptr || !is_device_pointer(out_offsets), "out_offsets must be host memory");
+  // tree->radiusSearch(point, float(cluster_tolerance_)) (extract_clusters.hpp:177) keeps d2 < float(r * r)
+  // (kdtree_flann.hpp:398); a square of 0 finds nothing, not even the point itself
+  const double r = double(float(tolerance));
+  const float t = float(r * r);
+  return euclidean_clusters(ix, t, min_size, max_size, out_labels, out_offsets, offsets_capacity, out_indices,
+                            indices_capacity, n_clusters, n_clustered);
+}
+
+void pclhip_index_last_cluster_stats(const pclhip_index* ix, double* hook_ms, double* flatten_ms, uint64_t* unions) {
+  if (hook_ms) *hook_ms = ix ? ix->cluster_ms[0] : 0.0;
+  if (flatten_ms) *flatten_ms = ix ? ix->cluster_ms[1] : 0.0;
+  if (unions) *unions = ix ? ix->cluster_unions : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 void pclhip_icp_params_default(pclhip_icp_params* p) {
   if (!p) return;

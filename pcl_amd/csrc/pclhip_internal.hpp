@@ -284,6 +284,8 @@ struct pclhip_index {
   double build_ms = 0;
   double last_kernel_ms = 0;
   double fpfh_pass_ms[2] = {0, 0};  // the SPFH and the weighting kernel of the last pclhip_fpfh
+  double cluster_ms[2] = {0, 0};    // the hook and the flatten kernel of the last pclhip_euclidean_clusters
+  uint64_t cluster_unions = 0;      // ... and the unions its hook kernel attempted
   bool has_normals = false;
   bool scaled = false;              // built through a rescaling point representation: coordinates * scale
   float scale[3] = {1, 1, 1};
@@ -565,6 +567,14 @@ pclhip_status outlier_filter(pclhip_index* ix, const int32_t* indices, uint64_t 
 // rows per original record to out_spfh (optional)
 pclhip_status fpfh_compute(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius, void* out,
                            size_t out_stride, float* out_spfh, uint64_t* out_nan_count);
+// EuclideanClusterExtraction over the index (cluster.hpp, compiled into radius.hip): the components of d2 < t
+pclhip_status euclidean_clusters(pclhip_index* ix, float t, uint32_t min_size, uint32_t max_size, int32_t* out_labels,
+                                 uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices,
+                                 uint64_t indices_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+// voxelgrid.hip's stable LSD radix passes (8 bits each) over n (key, value) pairs, ping-pong between (k0, v0) and (k1, v1);
+// iota: the values start as 0 .. n - 1.  Stream-ordered; the sorted arrays are one of the two pairs.
+pclhip_status radix_sort_pairs(pclhip_ctx* ctx, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, int bits,
+                               bool iota, uint32_t** keys_sorted, uint32_t** vals_sorted);
 // NormalDistributionsTransform: the voxel Gaussians of a target cloud (ndt_cells.hpp, compiled into voxelgrid.hip), in
 // ascending voxel id.  Device arrays owned by the struct (ndt_free_cells).
 struct NdtCells {

@@ -434,5 +434,8 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // FPFHEstimation: two radius traversals of the index with per-point histograms
 #include "fpfh.hpp"
 
+// EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
+#include "cluster.hpp"
+
 // SampleConsensusPrerejective: its scoring pass is a bounded 1-NN traversal of the target index
 #include "scp.hpp"

@@ -589,6 +589,37 @@ __global__ __launch_bounds__(256) void vg_centroid_row_kernel(const void* pts, s
 }
 
 }  // namespace
+
+// The stable LSD passes above for another caller (cluster.hpp): sorts n (key, value) pairs by the low `bits` bits of the
+// keys, ping-pong between (k0, v0) and (k1, v1); iota: the values start as 0 .. n - 1 and v0 is only written.  Stream-ordered.
+pclhip_status radix_sort_pairs(pclhip_ctx* ctx, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, int bits,
+                               bool iota, uint32_t** keys_sorted, uint32_t** vals_sorted) {
+  hipStream_t s = ctx->stream;
+  const uint32_t sort_blocks = (n + uint32_t(RS_KPB) - 1u) / uint32_t(RS_KPB);
+  DeviceScope scope(ctx);
+  uint32_t *hist = nullptr, *first = nullptr, *rowtot = nullptr;
+  if (n > 0) {
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&hist, size_t(256) * sort_blocks * 4));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&first, size_t(256) * sort_blocks * 4));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&rowtot, size_t(256) * 4));
+  }
+  bool first_pass = true;
+  for (int shift = 0; n > 0 && shift < bits; shift += 8) {
+    hipLaunchKernelGGL(rs_hist_kernel, dim3(sort_blocks), dim3(RS_THREADS), 0, s, k0, n, shift, sort_blocks, hist);
+    hipLaunchKernelGGL(rs_rowscan_kernel, dim3(256), dim3(256), 0, s, hist, sort_blocks, first, rowtot);
+    hipLaunchKernelGGL(rs_scatter_kernel, dim3(sort_blocks), dim3(RS_THREADS), 0, s, k0,
+                       (first_pass && iota) ? static_cast<const uint32_t*>(nullptr) : v0, n, shift, sort_blocks, first, rowtot,
+                       k1, v1);
+    PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+    std::swap(k0, k1);
+    std::swap(v0, v1);
+    first_pass = false;
+  }
+  *keys_sorted = k0;
+  *vals_sorted = v0;
+  return PCLHIP_OK;
+}
+
 void preload_voxelgrid_kernels() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(vg_key_kernel));
