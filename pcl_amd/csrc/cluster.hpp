@@ -7,8 +7,8 @@
 //
 // Pipeline (one stream, one read-back: the two counts):
 //   cluster_init_kernel     parent[pos] = pos
-//   cluster_hook_kernel     traverse<ClusterHook, true> with the fixed bound t; a hit at position j < own position i unites i
-//                           and j: both roots by path halving, the larger root hooked under the smaller by compare-and-swap
+//   cluster_hook_kernel     traverse<ClusterHook, true> with the fixed bound t (strict: traverse.hpp's leaf_hits_lt), one lane
+//                           per indexed point (for_each_query_group); a hit at position j < own position i unites i and j: both roots by path halving, the larger root hooked under the smaller by compare-and-swap
 //   cluster_flatten_kernel  (a launch of its own: the kernel boundary is what makes the hooks visible) parent[pos] = root(pos)
 //                           = the smallest kd position of the component, whatever the interleaving of the hook launch was
 //   cluster_count_kernel    per root: size (atomicAdd) and smallest original index (atomicMin): integers, order-free
@@ -22,7 +22,9 @@
 //   ascending, side by side in rank order.  No output position is an atomic ticket.
 #pragma once
 
-#include "outlier.hpp"
+#include "device_scan.hpp"
+#include "outlier.hpp"  // OR_BLOCK, OR_WAVES, outlier_grid, or_blocks
+#include "traverse.hpp"
 
 namespace pclhip {
 namespace {
@@ -97,7 +99,7 @@ struct ClusterHook {
     const uint32_t base = leaf_id * uint32_t(LEAF);
     if (base >= self) return;
     const float4* s = reinterpret_cast<const float4*>(buf) + slot;  // transposed staging
-    uint32_t mask = fpfh_hits<16>(s, qx[0], qy[0], qz[0], t);
+    uint32_t mask = leaf_hits_lt<16>(s, qx[0], qy[0], qz[0], t);
     if (self - base < uint32_t(LEAF)) mask &= (1u << (self - base)) - 1u;  // the own leaf: the slots below the lane's
     while (mask != 0) {
       const uint32_t j = base + uint32_t(__builtin_ctz(mask));
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(OR_BLOCK) void cluster_init_kernel(uint32_t* __rest
   if (i < n) parent[i] = i;
 }
 
-// One lane per indexed point, the group loop of ror_count_kernel.  The own leaf is not evaluated ahead of the walk as
+// One lane per indexed point (for_each_query_group).  The own leaf is not evaluated ahead of the walk as
 // ror_count_kernel does: the bound is fixed, so nothing is gained for the walk and the union code would exist twice -- the
 // own leaf only names the node the walk starts under, as in fpfh_spfh_kernel.
 // No wave waits for another: every loop is a find (ends at a root), a retry of a lost compare-and-swap, or the walk.
@@ -126,29 +128,19 @@ __global__ __launch_bounds__(OR_BLOCK) void cluster_hook_kernel(IndexView ix, fl
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   load_top_cache(ix, topbox_s);
   const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (ix.n + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
   ClusterHook pol;
   pol.t = t;
   pol.parent = parent;
   pol.unions = 0;
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t pos = g * WAVE + lane;
-    const bool real = pos < ix.n;
-    float4 p = make_float4(0, 0, 0, 0);
-    if (real) p = ix.pts[pos];
+  for_each_query_group(ix, nullptr, ix.n, [&](uint32_t pos, bool real, float4 p) {
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     const bool vv[1] = {real};
-    pol.self = real ? pos : 0u;  // (position 0 has no lower neighbour: a lane without a point tests nothing)
+    pol.self = pos;  // (0 for a lane without a point: position 0 has no lower neighbour, such a lane tests nothing)
     pol.root = pol.self;
     const uint32_t start = uniform_u32(pos / LEAF);  // lane 0 always holds a point
     traverse<ClusterHook, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
-  }
+  });
   uint32_t u = pol.unions;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) u += __shfl_xor(u, o);

@@ -17,7 +17,8 @@
 //                        float products in float in ascending distance: the result sits inside that sum's own rounding),
 //                        then every histogram is scaled by 100.0 / its sum in double (fpfh.hpp:161-177).  Rows in kd order.
 //   fpfh_emit_kernel     rows -> the caller's records in query order; NaN for records the index dropped
-// Both walks are traverse<Policy, true> (lane-sparse) with a fixed bound.  The lane's own leaf is NOT evaluated ahead of the
+// Both walks are traverse<Policy, true> (lane-sparse) with a fixed bound, the strict hit mask of traverse.hpp's leaf_hits_lt,
+// inside traverse.hpp's one-lane-per-point group loop (for_each_query_group).  The lane's own leaf is NOT evaluated ahead of the
 // walk as ror_count_kernel does: a fixed radius gains no bound from it, and the pair code would exist twice; the own leaf
 // only names the node the walk starts under.
 //
@@ -26,7 +27,9 @@
 // hist_incr = 100 / (neighbours - 1).
 #pragma once
 
-#include "outlier.hpp"
+#include "device_scan.hpp"
+#include "outlier.hpp"  // OR_BLOCK, OR_WAVES, outlier_grid, or_blocks, outlier_pos_kernel, outlier_compact_kernel
+#include "traverse.hpp"
 
 namespace pclhip {
 namespace {
@@ -89,38 +92,6 @@ __device__ __forceinline__ void fpfh_pair_bins(float px, float py, float pz, flo
   b3 = fpfh_bin((double(f3) + 1.0) * 0.5);
 }
 
-// bit c of the result: candidate c of the leaf block (chunk k of 16 bytes at s[k * STRIDE]) lies within d2 < t
-template <int STRIDE>
-__device__ __forceinline__ uint32_t fpfh_hits(const float4* s, float qx, float qy, float qz, float t) {
-  const v2f qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
-  uint32_t mask = 0;
-#pragma unroll
-  for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-    const float4 X = s[c4 * STRIDE], Y = s[(4 + c4) * STRIDE], Z = s[(8 + c4) * STRIDE];
-    v2f r0, r1;
-    {
-      const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-      r0 = dx * dx;
-      r0 = r0 + dy * dy;
-      r0 = r0 + dz * dz;
-    }
-    {
-      const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-      r1 = dx * dx;
-      r1 = r1 + dy * dy;
-      r1 = r1 + dz * dz;
-    }
-    mask |= ((r0.x < t ? 1u : 0u) | (r0.y < t ? 2u : 0u) | (r1.x < t ? 4u : 0u) | (r1.y < t ? 8u : 0u)) << (4 * c4);
-  }
-  return mask;
-}
-
-// coordinate `axis` of candidate j of a staged leaf block
-template <int STRIDE>
-__device__ __forceinline__ float fpfh_coord(const float4* s, int axis, uint32_t j) {
-  return reinterpret_cast<const float*>(s + (4 * axis + int(j >> 2)) * STRIDE)[j & 3u];
-}
-
 // Pass 1.  A lane walks the candidates of a leaf that passed d2 < t one after the other (its own hit mask: a round costs
 // the largest number of hits among the lanes, not 16 pair evaluations).
 struct FpfhSpfh {
@@ -138,7 +109,7 @@ struct FpfhSpfh {
                                             const float* qy, const float* qz) {
     if (leaf_id == NO_INDEX) return;
     const float4* s = reinterpret_cast<const float4*>(buf) + slot;  // transposed staging
-    uint32_t mask = fpfh_hits<16>(s, qx[0], qy[0], qz[0], t);
+    uint32_t mask = leaf_hits_lt<16>(s, qx[0], qy[0], qz[0], t);
     cnt += uint32_t(__builtin_popcount(mask));
     const uint32_t base = leaf_id * uint32_t(LEAF);
     if (base == (self & ~uint32_t(LEAF - 1))) mask &= ~(1u << (self & uint32_t(LEAF - 1)));
@@ -148,7 +119,7 @@ struct FpfhSpfh {
       const float4 n2 = nrm[base + j];
       if (!(isfinite(n2.x) && isfinite(n2.y) && isfinite(n2.z))) continue;
       int b1, b2, b3;
-      fpfh_pair_bins(px, py, pz, nx, ny, nz, fpfh_coord<16>(s, 0, j), fpfh_coord<16>(s, 1, j), fpfh_coord<16>(s, 2, j),
+      fpfh_pair_bins(px, py, pz, nx, ny, nz, leaf_coord<16>(s, 0, j), leaf_coord<16>(s, 1, j), leaf_coord<16>(s, 2, j),
                      n2.x, n2.y, n2.z, b1, b2, b3);
       col[b1 * WAVE] += 1;
       col[(FPFH_BINS + b2) * WAVE] += 1;
@@ -165,25 +136,14 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_spfh_kernel(IndexView ix, float
   __shared__ uint16_t hist_s[OR_WAVES][FPFH_DIM][WAVE];
   load_top_cache(ix, topbox_s);
   const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (ix.n + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
   FpfhSpfh pol;
   pol.t = t;
   pol.nrm = ix.nrm;
   pol.col = &hist_s[threadIdx.x / WAVE][0][lane];
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t pos = g * WAVE + lane;
-    const bool real = pos < ix.n;
-    float4 p = make_float4(0, 0, 0, 0), nq = make_float4(0, 0, 0, 0);
-    if (real) {
-      p = ix.pts[pos];
-      nq = ix.nrm[pos];
-    }
+  for_each_query_group(ix, nullptr, ix.n, [&](uint32_t pos, bool real, float4 p) {
+    float4 nq = make_float4(0, 0, 0, 0);
+    if (real) nq = ix.nrm[pos];
     const bool fin = real && isfinite(nq.x) && isfinite(nq.y) && isfinite(nq.z);
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     const bool vv[1] = {fin};
@@ -196,11 +156,11 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_spfh_kernel(IndexView ix, float
     const uint32_t start = uniform_u32(pos / LEAF);  // lane 0 always holds a point
     if (t > 0.0f)  // (t == 0: nothing lies within d2 < 0, the counters stay at zero)
       traverse<FpfhSpfh, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
-    if (!real) continue;
+    if (!real) return;
     float* row = spfh + size_t(pos) * FPFH_DIM;
     if (!fin) {
       for (int b = 0; b < FPFH_DIM; ++b) row[b] = __builtin_nanf("");
-      continue;
+      return;
     }
     const uint32_t others = pol.cnt > 0u ? pol.cnt - 1u : 0u;  // (cnt == 0 only with t == 0: the point misses itself)
     if (others > FPFH_MAX_COUNT) *overflow = 1u;  // a bin may have wrapped: the call fails
@@ -211,7 +171,7 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_spfh_kernel(IndexView ix, float
       for (uint32_t k = 0; k < c; ++k) v = __fadd_rn(v, incr);
       row[b] = v;
     }
-  }
+  });
 }
 
 // Pass 2: acc[b] += double(row[b]) * double(1.0f / d2) over the neighbours with d2 != 0 (the point itself and its exact
@@ -228,11 +188,11 @@ struct FpfhWeight {
                                             const float* qy, const float* qz) {
     if (leaf_id == NO_INDEX) return;
     const float4* s = reinterpret_cast<const float4*>(buf) + slot;
-    uint32_t mask = fpfh_hits<16>(s, qx[0], qy[0], qz[0], t);
+    uint32_t mask = leaf_hits_lt<16>(s, qx[0], qy[0], qz[0], t);
     while (mask != 0) {
       const uint32_t j = uint32_t(__builtin_ctz(mask));
       mask &= mask - 1u;
-      const float d2 = l2_simple(qx[0], qy[0], qz[0], fpfh_coord<16>(s, 0, j), fpfh_coord<16>(s, 1, j), fpfh_coord<16>(s, 2, j));
+      const float d2 = l2_simple(qx[0], qy[0], qz[0], leaf_coord<16>(s, 0, j), leaf_coord<16>(s, 1, j), leaf_coord<16>(s, 2, j));
       const float* row = spfh + (size_t(leaf_id) * LEAF + j) * FPFH_DIM;
       if (d2 == 0.0f || isnan(row[0])) continue;
       const double w = double(__fdiv_rn(1.0f, d2));
@@ -248,23 +208,11 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_weight_kernel(IndexView ix, con
   __shared__ WaveLdsBoxT<3072> wl_s[OR_WAVES];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   load_top_cache(ix, topbox_s);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (nq + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
-  FpfhWeight pol;
-  pol.t = t;
-  pol.spfh = spfh;
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t i = g * WAVE + lane;
-    const bool real = i < nq;
-    const uint32_t pos = real ? (qpos ? qpos[i] : i) : 0u;
-    float4 p = make_float4(0, 0, 0, 0);
-    if (real) p = ix.pts[pos];
+  for_each_query_group(ix, qpos, nq, [&](uint32_t pos, bool real, float4 p) {
+    FpfhWeight pol;
+    pol.t = t;
+    pol.spfh = spfh;
     const bool fin = real && !isnan(spfh[size_t(pos) * FPFH_DIM]);  // the point's own normal is finite
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     const bool vv[1] = {fin};
@@ -274,10 +222,10 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_weight_kernel(IndexView ix, con
     if (!(t > 0.0f)) {  // no neighbour, not even the query itself: the reference divides by the sum of no weights
       if (real)
         for (int b = 0; b < FPFH_DIM; ++b) fpfh[size_t(pos) * FPFH_DIM + b] = __builtin_nanf("");
-      continue;
+      return;
     }
     traverse<FpfhWeight, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
-    if (!real) continue;
+    if (!real) return;
     float* row = fpfh + size_t(pos) * FPFH_DIM;
 #pragma unroll
     for (int h = 0; h < 3; ++h) {
@@ -288,7 +236,7 @@ __global__ __launch_bounds__(OR_BLOCK) void fpfh_weight_kernel(IndexView ix, con
 #pragma unroll
       for (int b = 0; b < FPFH_BINS; ++b) row[h * FPFH_BINS + b] = fin ? float(pol.acc[h * FPFH_BINS + b] * f) : __builtin_nanf("");
     }
-  }
+  });
 }
 
 // value b of entry j <- row of record idx[j] (or j); NaN where the index holds no such point.  Rows whose first value is

@@ -13,12 +13,16 @@
 // Every pass streams the pair records once; the serial part (Hessian assembly, 6x6 eigen-solve, alpha, the gradient and
 // delta tests: gicp_forms.hpp) runs on the host between passes.  Sums: per thread in a fixed order, then the fixed-order
 // block sums of block_sums.hpp (rows of 64 doubles).
+// From search.hip itself, which must have defined them above its #include of this file: the launch geometry BLOCK and
+// WAVES_PER_BLOCK, and the launchers launch_icp_iterate and launch_gicp_covariances (declared in pclhip_internal.hpp).
 #pragma once
 
+#include <cfloat>
 #include <chrono>
 
 #include "block_sums.hpp"
 #include "gicp_forms.hpp"
+#include "icp_xform.hpp"
 
 struct pclhip_gicp {
   pclhip_ctx* ctx = nullptr;

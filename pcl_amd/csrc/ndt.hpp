@@ -349,6 +349,8 @@ pclhip_status ndt_copy_records(pclhip_ctx* ctx, const void* points, size_t strid
 }  // namespace
 }  // namespace pclhip
 
+using namespace pclhip;
+
 extern "C" {
 
 void pclhip_ndt_params_default(pclhip_ndt_params* p) {

@@ -17,6 +17,8 @@
 //   sor_finalize_kernel    the block sums -> mean, stddev, threshold on the device (both: the fixed order of block_sums.hpp)
 //   outlier_keep_kernel    classification; the keep flags are scanned (device_scan.hpp) and
 //   outlier_emit_kernel    writes the kept and removed ids, stable, in query order.
+// The three search kernels give every lane one query inside traverse.hpp's for_each_query_group; FPFH's and the clusters'
+// kernels (fpfh.hpp, cluster.hpp) run in the same loop and borrow this file's launch geometry.
 #pragma once
 
 #include <algorithm>
@@ -86,20 +88,8 @@ __global__ __launch_bounds__(OR_BLOCK, SOR_MINW(K)) void sor_dist_kernel(IndexVi
   __shared__ WaveLdsBoxT<3072> wl_s[OR_WAVES];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   load_top_cache(ix, topbox_s);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (nq + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t i = g * WAVE + lane;
-    const bool valid = i < nq;
-    const uint32_t pos = valid ? (qpos ? qpos[i] : i) : 0u;
-    float4 p = make_float4(0, 0, 0, 0);
-    if (valid) p = ix.pts[pos];
+  for_each_query_group(ix, qpos, nq, [&](uint32_t pos, bool valid, float4 p) {
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     const bool vv[1] = {valid};
     TopKDist<K> dist;
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(OR_BLOCK, SOR_MINW(K)) void sor_dist_kernel(IndexVi
     const uint32_t start = uniform_u32(pos / LEAF);  // lane 0 always holds a query
     traverse<TopKDist<K>, true>(ix, qx, qy, qz, vv, dist, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
     if (valid) dpos[pos] = sor_mean_of<K>(dist.d, kk);
-  }
+  });
 }
 
 // K > 64: the kk smallest d2 in a per-thread binary max-heap of floats, heap[slot * nthreads + thread] (coalesced), then
@@ -176,24 +166,12 @@ __global__ __launch_bounds__(OR_BLOCK) void sor_dist_heap_kernel(IndexView ix, c
   __shared__ WaveLdsBoxT<LEAF_BATCH * LEAF_FLOATS * 4> wl_s[OR_WAVES];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   load_top_cache(ix, topbox_s);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (nq + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
   TopKDistHeap pol;
   pol.stride = size_t(gridDim.x) * OR_BLOCK;
   pol.heap = heap + size_t(blockIdx.x) * OR_BLOCK + threadIdx.x;
   pol.k = kk;
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t i = g * WAVE + lane;
-    const bool valid = i < nq;
-    const uint32_t pos = valid ? (qpos ? qpos[i] : i) : 0u;
-    float4 p = make_float4(0, 0, 0, 0);
-    if (valid) p = ix.pts[pos];
+  for_each_query_group(ix, qpos, nq, [&](uint32_t pos, bool valid, float4 p) {
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     const bool vv[1] = {valid};
     pol.init();
@@ -204,12 +182,13 @@ __global__ __launch_bounds__(OR_BLOCK) void sor_dist_heap_kernel(IndexView ix, c
       for (int c = 1; c < kk; ++c) s += sqrt(double(pol.at(c)));
       dpos[pos] = float(s / double(kk - 1));
     }
-  }
+  });
 }
 
 // RadiusOutlierRemoval: how many points of the index lie within d2 <= t, counted up to `need` = min_pts + 1 (the query
 // itself included).  A lane that has them reports a negative bound: the traversal neither stages nor hands it another
-// leaf, and a wave whose lanes are all done stops.  Lane-sparse evaluation, the own leaf first.
+// leaf, and a wave whose lanes are all done stops.  Lane-sparse evaluation, the own leaf first.  (Inclusive, where
+// traverse.hpp's leaf_hits_lt is strict: see there.)
 struct RorCount {
   float t;
   uint32_t need, cnt;
@@ -224,20 +203,8 @@ struct RorCount {
     uint32_t c = 0;
 #pragma unroll
     for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-      const float4 X = s[c4 * STRIDE], Y = s[(4 + c4) * STRIDE], Z = s[(8 + c4) * STRIDE];
       v2f r0, r1;
-      {
-        const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-        r0 = dx * dx;
-        r0 = r0 + dy * dy;
-        r0 = r0 + dz * dz;
-      }
-      {
-        const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-        r1 = dx * dx;
-        r1 = r1 + dy * dy;
-        r1 = r1 + dz * dz;
-      }
+      quad_dist<STRIDE>(s, c4, qx2, qy2, qz2, r0, r1);
       c += (r0.x <= t ? 1u : 0u) + (r0.y <= t ? 1u : 0u) + (r1.x <= t ? 1u : 0u) + (r1.y <= t ? 1u : 0u);
     }
     cnt += c;
@@ -258,20 +225,8 @@ __global__ __launch_bounds__(OR_BLOCK) void ror_count_kernel(IndexView ix, const
   __shared__ WaveLdsBoxT<3072> wl_s[OR_WAVES];
   __shared__ Box topbox_s[TOPCACHE_BOXES];
   load_top_cache(ix, topbox_s);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const uint32_t ngroups = (nq + WAVE - 1) / WAVE;
-  const GroupSchedule sched(ngroups);
   TraverseStats ts;
-  GroupFeed feed(sched, ix.sched_ctr);
-  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
-    const uint32_t g = sched.global(gl);
-    if (g >= ngroups) break;
-    feed.ahead(gl);
-    const uint32_t i = g * WAVE + lane;
-    const bool valid = i < nq;
-    const uint32_t pos = valid ? (qpos ? qpos[i] : i) : 0u;
-    float4 p = make_float4(0, 0, 0, 0);
-    if (valid) p = ix.pts[pos];
+  for_each_query_group(ix, qpos, nq, [&](uint32_t pos, bool valid, float4 p) {
     const float qx[1] = {p.x}, qy[1] = {p.y}, qz[1] = {p.z};
     RorCount pol;
     pol.t = t;
@@ -282,7 +237,7 @@ __global__ __launch_bounds__(OR_BLOCK) void ror_count_kernel(IndexView ix, const
     const uint32_t start = uniform_u32(pos / LEAF);
     traverse<RorCount, true>(ix, qx, qy, qz, vv, pol, wl_s[threadIdx.x / WAVE], topbox_s, ts, start);
     if (valid) enough[pos] = pol.cnt >= need ? 1u : 0u;
-  }
+  });
 }
 
 // per entry: the distance in query order (0 for a non-finite record) and per block (sum d, sum fl(d*d), valid) in double.

@@ -214,6 +214,49 @@ __device__ __forceinline__ v2f pair_dist(const float* l, int j, v2f qx2, v2f qy2
   return r;
 }
 
+// The same distances for a lane that reads a leaf block of its own, 16-byte chunk k at s[k * STRIDE] (16: the transposed
+// staging of traverse(): SPARSE; 1: the index's SoA copy): candidates 4 * c4 + {0, 1} in r0, + {2, 3} in r1.  The
+// policies that look at a block lane by lane take their distances from here: one operation order, one place (NN1MinT
+// alone keeps its copy: see its leaf_at).
+template <int STRIDE>
+__device__ __forceinline__ void quad_dist(const float4* s, int c4, v2f qx2, v2f qy2, v2f qz2, v2f& r0, v2f& r1) {
+  const float4 X = s[c4 * STRIDE], Y = s[(4 + c4) * STRIDE], Z = s[(8 + c4) * STRIDE];
+  {
+    const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
+    r0 = dx * dx;
+    r0 = r0 + dy * dy;
+    r0 = r0 + dz * dz;
+  }
+  {
+    const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
+    r1 = dx * dx;
+    r1 = r1 + dy * dy;
+    r1 = r1 + dz * dz;
+  }
+}
+
+// bit c of the result: candidate c of such a block lies within d2 < t.  STRICT, the relation of radiusSearch (FPFH's
+// neighbourhoods, the clusters' edges); RadiusOutlierRemoval counts d2 <= t, inclusive, and keeps a count of its own
+// (outlier.hpp: RorCount) on the same quad_dist.
+template <int STRIDE>
+__device__ __forceinline__ uint32_t leaf_hits_lt(const float4* s, float qx, float qy, float qz, float t) {
+  const v2f qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
+  uint32_t mask = 0;
+#pragma unroll
+  for (int c4 = 0; c4 < LEAF / 4; ++c4) {
+    v2f r0, r1;
+    quad_dist<STRIDE>(s, c4, qx2, qy2, qz2, r0, r1);
+    mask |= ((r0.x < t ? 1u : 0u) | (r0.y < t ? 2u : 0u) | (r1.x < t ? 4u : 0u) | (r1.y < t ? 8u : 0u)) << (4 * c4);
+  }
+  return mask;
+}
+
+// coordinate `axis` (0 x, 1 y, 2 z) of candidate j of such a block
+template <int STRIDE>
+__device__ __forceinline__ float leaf_coord(const float4* s, int axis, uint32_t j) {
+  return reinterpret_cast<const float*>(s + (4 * axis + int(j >> 2)) * STRIDE)[j & 3u];
+}
+
 // ---- leaf policies -------------------------------------------------------------------------------
 // All policies see a staged leaf block `l` in LDS and the leaf id; every lane runs them.
 //
@@ -369,6 +412,7 @@ struct NN1MinT {
       float m = __builtin_inff();
 #pragma unroll
       for (int c4 = 0; c4 < LEAF / 4; ++c4) {
+        // (quad_dist written out, here and in resolve(): through the helper the schedule of the ICP search kernels moves)
         const float4 X = s[c4 * STRIDE], Y = s[(LEAF / 4 + c4) * STRIDE], Z = s[(2 * (LEAF / 4) + c4) * STRIDE];
         {
           const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
@@ -500,20 +544,9 @@ struct TopKReg {
       const v2f qx2 = {qx[0], qx[0]}, qy2 = {qy[0], qy[0]}, qz2 = {qz[0], qz[0]};
 #pragma unroll
       for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-        const float4 X = s[c4 * 16], Y = s[(4 + c4) * 16], Z = s[(8 + c4) * 16], W = s[(12 + c4) * 16];
+        const float4 W = s[(12 + c4) * 16];
         v2f r0, r1;
-        {
-          const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-          r0 = dx * dx;
-          r0 = r0 + dy * dy;
-          r0 = r0 + dz * dz;
-        }
-        {
-          const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-          r1 = dx * dx;
-          r1 = r1 + dy * dy;
-          r1 = r1 + dz * dz;
-        }
+        quad_dist<16>(s, c4, qx2, qy2, qz2, r0, r1);
         const float ds[4] = {r0.x, r0.y, r1.x, r1.y}, ws[4] = {W.x, W.y, W.z, W.w};
         const float m = __builtin_fminf(__builtin_fminf(ds[0], ds[1]), __builtin_fminf(ds[2], ds[3]));
         if (__builtin_amdgcn_ballot_w64(m <= key_dist(keys[K - 1])) == 0) continue;
@@ -583,20 +616,8 @@ struct TopKDist {
     float m = __builtin_inff();
 #pragma unroll
     for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-      const float4 X = s[c4 * STRIDE], Y = s[(4 + c4) * STRIDE], Z = s[(8 + c4) * STRIDE];
       v2f r0, r1;
-      {
-        const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-        r0 = dx * dx;
-        r0 = r0 + dy * dy;
-        r0 = r0 + dz * dz;
-      }
-      {
-        const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-        r1 = dx * dx;
-        r1 = r1 + dy * dy;
-        r1 = r1 + dz * dz;
-      }
+      quad_dist<STRIDE>(s, c4, qx2, qy2, qz2, r0, r1);
       const float m4 = __builtin_fminf(__builtin_fminf(r0.x, r0.y), __builtin_fminf(r1.x, r1.y));
       m = __builtin_fminf(m, m4);
       // (skipping the four insertions when no active lane's list can change -- one ballot per chunk -- was measured:
@@ -665,20 +686,8 @@ struct CollectLE {
       const v2f qx2 = {qx[0], qx[0]}, qy2 = {qy[0], qy[0]}, qz2 = {qz[0], qz[0]};
 #pragma unroll
       for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-        const float4 X = s[c4 * STRIDE], Y = s[(4 + c4) * STRIDE], Z = s[(8 + c4) * STRIDE];
         v2f r0, r1;
-        {
-          const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-          r0 = dx * dx;
-          r0 = r0 + dy * dy;
-          r0 = r0 + dz * dz;
-        }
-        {
-          const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-          r1 = dx * dx;
-          r1 = r1 + dy * dy;
-          r1 = r1 + dz * dz;
-        }
+        quad_dist<STRIDE>(s, c4, qx2, qy2, qz2, r0, r1);
         take(r0.x, base + uint32_t(4 * c4));
         take(r0.y, base + uint32_t(4 * c4 + 1));
         take(r1.x, base + uint32_t(4 * c4 + 2));
@@ -706,20 +715,8 @@ struct CollectCodes {
       uint32_t over = 0;
 #pragma unroll
       for (int c4 = 0; c4 < LEAF / 4; ++c4) {
-        const float4 X = s[c4], Y = s[4 + c4], Z = s[8 + c4];
         v2f r0, r1;
-        {
-          const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
-          r0 = dx * dx;
-          r0 = r0 + dy * dy;
-          r0 = r0 + dz * dz;
-        }
-        {
-          const v2f dx = qx2 - v2f{X.z, X.w}, dy = qy2 - v2f{Y.z, Y.w}, dz = qz2 - v2f{Z.z, Z.w};
-          r1 = dx * dx;
-          r1 = r1 + dy * dy;
-          r1 = r1 + dz * dz;
-        }
+        quad_dist<1>(s, c4, qx2, qy2, qz2, r0, r1);
         const v2f u0 = t2 - r0, u1 = t2 - r1;
         over = __builtin_amdgcn_alignbit(over, __float_as_uint(u0.x), 31);  // (over << 1) | sign
         over = __builtin_amdgcn_alignbit(over, __float_as_uint(u0.y), 31);
@@ -1471,5 +1468,30 @@ struct GroupFeed {
   }
   __device__ __forceinline__ uint32_t advance() const { return asked_ ? resolve() : next_; }
 };
+
+// That simple loop for the kernels whose queries are points of the index itself, one per lane: query i of nq is the point at
+// sorted position qpos[i] (ascending, so a wave's 64 queries are spatially compact) or, with qpos == nullptr, at position
+// i.  body(pos, valid, p) runs once per group, all 64 lanes together (it may call traverse()): the lane's position, whether
+// it holds a query, and the point.  A lane behind the last query gets pos = 0, valid = false and a zero point; lane 0
+// always holds a query, so uniform_u32(pos / LEAF) names the leaf the walk of the group starts under.
+template <class Body>
+__device__ __forceinline__ void for_each_query_group(const IndexView& ix, const uint32_t* __restrict__ qpos, uint32_t nq,
+                                                     Body&& body) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const uint32_t ngroups = (nq + WAVE - 1) / WAVE;
+  const GroupSchedule sched(ngroups);
+  GroupFeed feed(sched, ix.sched_ctr);
+  for (uint32_t gl = feed.first(sched); gl != GroupFeed::END; gl = feed.advance()) {
+    const uint32_t g = sched.global(gl);
+    if (g >= ngroups) break;
+    feed.ahead(gl);
+    const uint32_t i = g * WAVE + lane;
+    const bool valid = i < nq;
+    const uint32_t pos = valid ? (qpos ? qpos[i] : i) : 0u;
+    float4 p = make_float4(0, 0, 0, 0);
+    if (valid) p = ix.pts[pos];
+    body(pos, valid, p);
+  }
+}
 
 }  // namespace pclhip

@@ -1,6 +1,6 @@
 """pclhip_fpfh off the path of tests/test_gpu_fpfh.py (bun0, one 5,003-point cloud, 200 points with edge records): clouds
 smaller than a leaf (16) and a wavefront (64), the strict bound d2 < float(r * r) of the FPFH walks' own comparison
-(fpfh_hits), radii whose float square is 0, the smallest subnormal and +inf, clouds far from the origin, duplicates en
+(leaf_hits_lt), radii whose float square is 0, the smallest subnormal and +inf, clouds far from the origin, duplicates en
 masse, an index with three box levels, a coplanar grid whose rows are known in closed form, and the object's state
 between calls.
 
