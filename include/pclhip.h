@@ -880,6 +880,77 @@ PCLHIP_API pclhip_status pclhip_scp_fitness_score(pclhip_scp* scp, const float T
 /* GPU time (ms) of the feature k-NN, hypothesis and fitness launches of the last pclhip_scp_align. */
 PCLHIP_API void pclhip_scp_last_ms(const pclhip_scp* scp, double* knn_ms, double* hypothesis_ms, double* fitness_ms);
 
+/* ---- SACSegmentation: SACMODEL_PLANE with SAC_RANSAC --------------------------------------------------
+ * Replaces pcl::SACSegmentation<PointT>::segment (segmentation/include/pcl/segmentation/impl/sac_segmentation.hpp:79-133)
+ * for SampleConsensusModelPlane (sample_consensus/.../impl/sac_model_plane.hpp:80-118,153-230,311-360) under
+ * RandomSampleConsensus (impl/ransac.hpp:56-217).  The point set is `indices` (positions into the cloud, any order,
+ * repeats allowed) or every record; n = its length; samples are positions in that list.
+ * Trial t = 0, 1, 2, ...: the sample is scp::select_samples(seed, t, 3, n) (the draws of SampleConsensusPrerejective
+ * above); with p0, p1, p2 the points at s[0] < s[1] < s[2], in float without contraction: c = (p1 - p0) x (p2 - p0),
+ * norm = sqrtf((cx cx + cy cy) + cz cz); norm < 1e-5f skips the trial; (a, b, c) = c / norm,
+ * d = -((a p0x + b p0y) + c p0z).  A point is an inlier when fabsf((a x + b y) + (c z + d)) < float(threshold): strict,
+ * float, the order of dist4 / dist8 (sac_model_plane.h:299-320), the one expression of counting, selecting and the
+ * refined selection.  A non-finite point is never an inlier; a sample that holds one is not a skip: its trial counts 0.
+ * The trials are replayed on the host in order (sac_replay.hpp): a skipped trial adds to `skipped` and ends the call at
+ * 10 * max_iterations; a count > best (strict: the earliest wins) becomes the model and sets
+ * k = log(1 - probability) / log(clamp(1 - (best / n)^3, DBL_EPSILON, 1 - DBL_EPSILON)); ++iterations; the call ends when
+ * iterations > k or iterations > max_iterations.  No trial with a count above 0: no model (out_coeff zeroed, no inliers,
+ * best_trial -1 in the stats); the outlier list is then the whole point set.
+ * With optimize_coefficients and more than 3 inliers the plane is refitted to the inliers: the nine sums of
+ * computeMeanAndCovarianceMatrix (shifted by the first inlier) in double in a fixed order, the covariance formed in double
+ * and rounded once to float, pcl::eigen33's smallest eigenvector in the reference's float order, d = -(n . centroid) in
+ * float; a non-finite result keeps the unrefined coefficients; the inliers are selected again with the result.
+ * Lists hold cloud indices in the order of the point set (ascending when no indices are given); the outlier list is its
+ * complement (ExtractIndices::setNegative(true)).  Outputs are host or device memory, each optional; the counts are always
+ * written, a capacity that is too small gives PCLHIP_ERR_OVERFLOW after them.  Two calls give the same bytes, and
+ * batch_size never changes a result.
+ * Deviations: the draws; a degenerate sample counts towards the skip limit (the reference redraws it up to 1,000 times
+ * inside getSamples first); the norm is a plain sqrtf (Eigen's stableNorm guards an underflow the 1e-5 test makes moot);
+ * one distance expression and float(threshold) everywhere (selectWithinDistance uses Eigen's dot and compares a float with
+ * a double); the refit's double tree sums replace a sequential float sum.
+ * Not built: other models and methods, setSamplesMaxDist, multi-GPU. */
+typedef struct {
+  double distance_threshold;        /* sac_segmentation.h:90, default 0.0 */
+  int max_iterations;               /* default 50 */
+  double probability;               /* default 0.99 */
+  int optimize_coefficients;        /* default 1 */
+  uint64_t seed;                    /* of the draws, default 0 */
+  int batch_size;                   /* trials per scoring pass (<= 1024); 0 (default): 64 first, then doubling */
+} pclhip_sac_plane_params;
+typedef struct {
+  uint64_t trials;                  /* trials the replay consumed (the draw counter at the end) */
+  int iterations;                   /* iterations_ */
+  uint32_t skipped;                 /* degenerate samples */
+  int batches;                      /* scoring passes */
+  int best_trial;                   /* the winner; -1: no model */
+  uint32_t best_count;              /* its count (the unrefined inliers) */
+  int refined;                      /* the refit replaced the coefficients */
+  double count_ms;                  /* GPU time of the scoring launches (HIP events) */
+  double total_ms;                  /* GPU time of the whole call */
+} pclhip_sac_plane_stats;
+typedef struct {                    /* one entry per consumed trial (pclhip_sac_last_trace) */
+  int samples[3];                   /* ascending positions in the point set */
+  int skipped;
+  float coefficients[4];            /* as computed (not finite for a sample that holds a non-finite point) */
+  uint32_t count;                   /* 0 for a skipped trial */
+} pclhip_sac_plane_trace;
+PCLHIP_API void pclhip_sac_plane_params_default(pclhip_sac_plane_params* p);
+PCLHIP_API pclhip_status pclhip_sac_segment_plane(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                  const int32_t* indices, uint64_t n_indices,
+                                                  const pclhip_sac_plane_params* params, float out_coeff[4],
+                                                  int32_t* out_inliers, uint64_t inliers_capacity, uint64_t* out_n_inliers,
+                                                  int32_t* out_outliers, uint64_t outliers_capacity,
+                                                  uint64_t* out_n_outliers, pclhip_sac_plane_stats* out_stats);
+/* SampleConsensusModelPlane::countWithinDistance for n_models coefficient quadruples (host) in batched passes over the
+ * point set: out_counts[m] (host) points with fabsf((a x + b y) + (c z + d)) < float(threshold) (exposed for tests). */
+PCLHIP_API pclhip_status pclhip_sac_plane_evaluate(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                   const int32_t* indices, uint64_t n_indices, double threshold,
+                                                   const float* coeffs, int n_models, uint32_t* out_counts);
+/* The trials the last pclhip_sac_segment_plane of this context consumed (the first 65,536 at most): *count always, the
+ * first min(capacity, *count) records to buf (host). */
+PCLHIP_API pclhip_status pclhip_sac_last_trace(pclhip_ctx* ctx, pclhip_sac_plane_trace* buf, uint64_t capacity,
+                                               uint64_t* count);
+
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/
  * voxel_grid.hpp:597-814) with downsample_all_data and the optional pass-through filter in front of

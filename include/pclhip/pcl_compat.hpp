@@ -1966,4 +1966,83 @@ class EuclideanClusterExtraction : public PCLBase<PointT> {
   std::string error_;
 };
 
+// ---- pcl::ModelCoefficients (common/include/pcl/ModelCoefficients.h; `values` only), the model and method constants
+// (sample_consensus/model_types.h:45-47, method_types.h:45) and pcl::SACSegmentation<PointT> (segmentation/include/pcl/
+// segmentation/sac_segmentation.h:77-330, impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC over
+// pclhip_sac_segment_plane.  Any other model or method leaves both outputs empty and says so in getLastError().
+struct ModelCoefficients {
+  using Ptr = std::shared_ptr<ModelCoefficients>;
+  using ConstPtr = std::shared_ptr<const ModelCoefficients>;
+  std::vector<float> values;
+};
+enum SacModel { SACMODEL_PLANE = 0 };
+constexpr int SAC_RANSAC = 0;
+
+template <typename PointT>
+class SACSegmentation : public PCLBase<PointT> {
+ public:
+  SACSegmentation() : SACSegmentation(Context::defaultContext()) {}
+  explicit SACSegmentation(Context::Ptr ctx) : ctx_(std::move(ctx)) { pclhip_sac_plane_params_default(&params_); }
+  void setModelType(int model) { model_type_ = model; }
+  int getModelType() const { return model_type_; }
+  void setMethodType(int method) { method_type_ = method; }
+  int getMethodType() const { return method_type_; }
+  void setDistanceThreshold(double threshold) { params_.distance_threshold = threshold; }
+  double getDistanceThreshold() const { return params_.distance_threshold; }
+  void setMaxIterations(int max_iterations) { params_.max_iterations = max_iterations; }
+  int getMaxIterations() const { return params_.max_iterations; }
+  void setProbability(double probability) { params_.probability = probability; }
+  double getProbability() const { return params_.probability; }
+  void setOptimizeCoefficients(bool optimize) { params_.optimize_coefficients = optimize ? 1 : 0; }
+  bool getOptimizeCoefficients() const { return params_.optimize_coefficients != 0; }
+  // the draws are a pure function of (seed, trial, slot): include/pclhip.h
+  void setSeed(std::uint64_t seed) { params_.seed = seed; }
+  std::uint64_t getSeed() const { return params_.seed; }
+  const std::string& getLastError() const { return error_; }
+  const pclhip_sac_plane_stats& getLastStats() const { return stats_; }
+  // the entries of the point set the last segment() left over, in its order (ExtractIndices::setNegative(true))
+  const Indices& getOutliers() const { return outliers_; }
+
+  void segment(PointIndices& inliers, ModelCoefficients& model_coefficients) {
+    inliers.indices.clear();
+    model_coefficients.values.clear();
+    outliers_.clear();
+    error_.clear();
+    stats_ = pclhip_sac_plane_stats();
+    stats_.best_trial = -1;
+    if (model_type_ != SACMODEL_PLANE || method_type_ != SAC_RANSAC) {
+      error_ = "SACSegmentation: only SACMODEL_PLANE with SAC_RANSAC is built";
+      return;
+    }
+    if (!this->input_ || this->input_->empty() || !ctx_ || !ctx_->ok()) return;
+    const bool subset = this->indices_ && !this->fake_indices_;
+    if (subset && this->indices_->empty()) return;
+    const std::size_t n = this->input_->size(), m = subset ? this->indices_->size() : n;
+    Indices in(m), out(m);
+    float coeff[4] = {0, 0, 0, 0};
+    std::uint64_t n_in = 0, n_out = 0;
+    if (pclhip_sac_segment_plane(ctx_->get(), this->input_->points.data(), n, sizeof(PointT),
+                                 subset ? this->indices_->data() : nullptr, subset ? m : 0, &params_, coeff, in.data(), m, &n_in,
+                                 out.data(), m, &n_out, &stats_) != PCLHIP_OK) {
+      error_ = pclhip_last_error(ctx_->get());
+      return;
+    }
+    out.resize(std::size_t(n_out));
+    outliers_.swap(out);
+    if (stats_.best_trial < 0) return;  // no model: both stay empty (impl/sac_segmentation.hpp:106-114)
+    in.resize(std::size_t(n_in));
+    inliers.indices.swap(in);
+    model_coefficients.values.assign(coeff, coeff + 4);
+  }
+
+ private:
+  Context::Ptr ctx_;
+  pclhip_sac_plane_params params_;
+  pclhip_sac_plane_stats stats_ = pclhip_sac_plane_stats();
+  int model_type_ = -1;  // sac_segmentation.h:83-84
+  int method_type_ = 0;
+  Indices outliers_;
+  std::string error_;
+};
+
 }  // namespace pclhip

@@ -3,12 +3,13 @@ VoxelGrid) behind PCL's plugin surface.  Compute lives in libpclhip.so (pcl_amd/
 behind the C ABI of include/pclhip.h; this package is the ctypes host mirror used by tests and
 bench.py.  The C++ mirror of the same surface is include/pclhip/pcl_compat.hpp."""
 from . import synth  # noqa: F401
-from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SYMMETRIC, PclHipError, PclHipUnavailable)  # noqa: F401
+from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_PLANE, SYMMETRIC, PclHipError,  # noqa: F401
+                   PclHipUnavailable)
 from .api import (Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
-                  RadiusOutlierRemoval, SampleConsensusPrerejective,
+                  RadiusOutlierRemoval, SACSegmentation, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

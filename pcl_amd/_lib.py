@@ -113,6 +113,24 @@ class ScpTrace(C.Structure):
                 ("transformation", C.c_float * 16), ("inliers", C.c_uint32), ("error", C.c_float)]
 
 
+class SacPlaneParams(C.Structure):
+    _fields_ = [("distance_threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
+                ("optimize_coefficients", C.c_int), ("seed", C.c_uint64), ("batch_size", C.c_int)]
+
+
+class SacPlaneStats(C.Structure):
+    _fields_ = [("trials", C.c_uint64), ("iterations", C.c_int), ("skipped", C.c_uint32), ("batches", C.c_int),
+                ("best_trial", C.c_int), ("best_count", C.c_uint32), ("refined", C.c_int), ("count_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+class SacPlaneTrace(C.Structure):
+    _fields_ = [("samples", C.c_int * 3), ("skipped", C.c_int), ("coefficients", C.c_float * 4), ("count", C.c_uint32)]
+
+
+SACMODEL_PLANE = 0   # sample_consensus/model_types.h:47
+SAC_RANSAC = 0       # sample_consensus/method_types.h:45
+
 NDT_RADIUS, NDT_DIRECT27, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = 0, 1, 2, 3, 4
 
 
@@ -222,6 +240,12 @@ SIGNATURES = {
     "pclhip_scp_fitness_score": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_double),
                                            C.POINTER(_u64)]),
     "pclhip_scp_last_ms": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pclhip_sac_plane_params_default": (None, [C.POINTER(SacPlaneParams)]),
+    "pclhip_sac_segment_plane": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, C.POINTER(SacPlaneParams), C.POINTER(C.c_float),
+                                           _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64),
+                                           C.POINTER(SacPlaneStats)]),
+    "pclhip_sac_plane_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, C.c_double, C.POINTER(C.c_float), C.c_int, _vp]),
+    "pclhip_sac_last_trace": (C.c_int, [_vp, C.POINTER(SacPlaneTrace), _u64, C.POINTER(_u64)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

@@ -8,6 +8,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
   pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
+  pcl::SACSegmentation (planes, RANSAC)                segmentation/include/pcl/segmentation/sac_segmentation.h:77-330
 Clouds are (n, c>=3) float32 arrays: numpy (host) or torch CUDA tensors (device-resident; only the
 pointer crosses the boundary).  All compute happens in libpclhip.so; there is no CPU fallback.
 """
@@ -2166,6 +2167,173 @@ class EuclideanClusterExtraction:
     def labels(self):
         """Per record of the cloud: the rank of its cluster in the last extract(), -1 for a record in no returned cluster."""
         return self._labels
+
+
+class SACSegmentation:
+    """pcl::SACSegmentation<PointT> (segmentation/include/pcl/segmentation/sac_segmentation.h:77-330,
+    impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC, over pclhip_sac_segment_plane.  The input is an
+    (n, c >= 3) float32 cloud, numpy or a torch CUDA tensor; the index lists come back in the same kind of array.  The draws
+    are a pure function of (seed, trial, slot) (include/pclhip.h): setSeed."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.p = _lib.SacPlaneParams()
+        self.lib.pclhip_sac_plane_params_default(C.byref(self.p))
+        self._model = -1       # sac_segmentation.h:83-84: neither is set by default
+        self._method = 0
+        self._cloud = None
+        self._indices = None
+        self._outliers = None
+        self._stats = None
+
+    def getClassName(self):
+        return "SACSegmentation"
+
+    def setModelType(self, model):
+        if int(model) != _lib.SACMODEL_PLANE:
+            raise NotImplementedError("SACSegmentation: only SACMODEL_PLANE is built")
+        self._model = int(model)
+
+    def getModelType(self):
+        return self._model
+
+    def setMethodType(self, method):
+        if int(method) != _lib.SAC_RANSAC:
+            raise NotImplementedError("SACSegmentation: only SAC_RANSAC is built")
+        self._method = int(method)
+
+    def getMethodType(self):
+        return self._method
+
+    def setDistanceThreshold(self, threshold):
+        self.p.distance_threshold = float(threshold)
+
+    def getDistanceThreshold(self):
+        return float(self.p.distance_threshold)
+
+    def setMaxIterations(self, n):
+        self.p.max_iterations = int(n)
+
+    def getMaxIterations(self):
+        return int(self.p.max_iterations)
+
+    def setProbability(self, probability):
+        self.p.probability = float(probability)
+
+    def getProbability(self):
+        return float(self.p.probability)
+
+    def setOptimizeCoefficients(self, optimize):
+        self.p.optimize_coefficients = int(bool(optimize))
+
+    def getOptimizeCoefficients(self):
+        return bool(self.p.optimize_coefficients)
+
+    def setSeed(self, seed):
+        self.p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def getSeed(self):
+        return int(self.p.seed)
+
+    def setBatchSize(self, n):
+        """Trials per scoring pass (0: automatic); never changes a result."""
+        self.p.batch_size = int(n)
+
+    def setInputCloud(self, cloud):
+        self._cloud = cloud
+
+    def getInputCloud(self):
+        return self._cloud
+
+    def setIndices(self, indices):
+        """PCLBase::setIndices: the point set, in this order (None: every record)."""
+        self._indices = indices
+
+    def getIndices(self):
+        return self._indices
+
+    def _inputs(self):
+        assert self._cloud is not None, "setInputCloud first"
+        if self._model != _lib.SACMODEL_PLANE:
+            raise ValueError("SACSegmentation: no model type was set (setModelType(SACMODEL_PLANE))")
+        ptr, stride, n, keep = _cloud(self._cloud)
+        idx, ip, ni = None, None, 0
+        if self._indices is not None:
+            if _is_torch(self._indices):
+                import torch
+                idx = self._indices.to(torch.int32).contiguous()
+                ip, ni = C.c_void_p(idx.data_ptr()), int(idx.numel())
+            else:
+                idx = np.ascontiguousarray(self._indices, np.int32).reshape(-1)
+                ip, ni = C.c_void_p(idx.ctypes.data), len(idx)
+            if ni == 0:  # an empty point set, not "every record"
+                idx = np.zeros(1, np.int32)
+                ip = C.c_void_p(idx.ctypes.data)
+        return ptr, stride, n, ip, ni, (keep, idx)
+
+    def segment(self, inliers_capacity=None, outliers_capacity=None):
+        """segment(PointIndices&, ModelCoefficients&) -> (inliers int32, coefficients float32 [4]); both empty when no model
+        was found.  getOutliers() gives the rest of the point set.  The capacities default to the size of the point set."""
+        ptr, stride, n, ip, ni, keep = self._inputs()
+        m = ni if self._indices is not None else n
+        cap_in = m if inliers_capacity is None else int(inliers_capacity)
+        cap_out = m if outliers_capacity is None else int(outliers_capacity)
+        if _is_torch(self._cloud):
+            import torch
+            inl = torch.empty(max(cap_in, 1), dtype=torch.int32, device=self._cloud.device)
+            outl = torch.empty(max(cap_out, 1), dtype=torch.int32, device=self._cloud.device)
+            pin, pout = C.c_void_p(inl.data_ptr()), C.c_void_p(outl.data_ptr())
+        else:
+            inl = np.empty(max(cap_in, 1), np.int32)
+            outl = np.empty(max(cap_out, 1), np.int32)
+            pin, pout = C.c_void_p(inl.ctypes.data), C.c_void_p(outl.ctypes.data)
+        coeff = np.zeros(4, np.float32)
+        n_in, n_out = C.c_uint64(0), C.c_uint64(0)
+        st = _lib.SacPlaneStats()
+        self._outliers = None
+        self._stats = None
+        rc = self.lib.pclhip_sac_segment_plane(self.ctx.h, ptr, n, stride, ip, ni, C.byref(self.p), _fp(coeff), pin, cap_in,
+                                               C.byref(n_in), pout, cap_out, C.byref(n_out), C.byref(st))
+        self._stats = dict(trials=int(st.trials), iterations=int(st.iterations), skipped=int(st.skipped),
+                           batches=int(st.batches), best_trial=int(st.best_trial), best_count=int(st.best_count),
+                           refined=bool(st.refined), count_ms=float(st.count_ms), total_ms=float(st.total_ms),
+                           n_inliers=int(n_in.value), n_outliers=int(n_out.value))
+        check(rc, self.ctx.h)
+        self._outliers = outl[:n_out.value]
+        if st.best_trial < 0:
+            return inl[:0], np.zeros(0, np.float32)
+        return inl[:n_in.value], coeff
+
+    def getOutliers(self):
+        """The entries of the point set (cloud indices) that the last segment() left over, in the set's order
+        (ExtractIndices::setNegative(true) on its inliers)."""
+        return self._outliers
+
+    def lastStats(self):
+        """dict of the last segment(): trials, iterations, skipped, batches, best_trial, best_count, refined, count_ms (GPU
+        time of the scoring launches), total_ms (GPU time of the call), n_inliers, n_outliers."""
+        return self._stats
+
+    def trace(self, capacity=65536):
+        """One dict per trial the last segment() consumed: samples, skipped, coefficients, count."""
+        n = C.c_uint64(0)
+        check(self.lib.pclhip_sac_last_trace(self.ctx.h, None, 0, C.byref(n)), self.ctx.h)
+        m = min(int(n.value), int(capacity))
+        buf = (_lib.SacPlaneTrace * max(1, m))()
+        check(self.lib.pclhip_sac_last_trace(self.ctx.h, buf, m, C.byref(n)), self.ctx.h)
+        return [dict(samples=list(t.samples), skipped=bool(t.skipped), coefficients=np.array(t.coefficients, np.float32),
+                     count=int(t.count)) for t in buf[:m]]
+
+    def countWithinDistance(self, models):
+        """SampleConsensusModelPlane::countWithinDistance of (H, 4) coefficient rows over the point set, batched ->
+        (H,) uint32."""
+        ptr, stride, n, ip, ni, keep = self._inputs()
+        M = np.ascontiguousarray(models, np.float32).reshape(-1, 4)
+        cnt = np.zeros(len(M), np.uint32)
+        check(self.lib.pclhip_sac_plane_evaluate(self.ctx.h, ptr, n, stride, ip, ni, float(self.p.distance_threshold), _fp(M),
+                                                 len(M), C.c_void_p(cnt.ctypes.data)), self.ctx.h)
+        return cnt
 
 
 def featureKSearch(ctx, target_rows, query_rows, k):

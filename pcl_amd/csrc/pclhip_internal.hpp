@@ -251,6 +251,8 @@ struct pclhip_ctx {
   size_t arena_bytes = 0;
   std::map<size_t, size_t> arena_free;  // offset -> bytes of the free ranges
   bool arena_tried = false;             // the automatic reservation was attempted (once per context)
+  // the trials the last pclhip_sac_segment_plane consumed (sac.hpp; pclhip_sac_last_trace)
+  std::vector<pclhip_sac_plane_trace> sac_trace;
 };
 
 struct pclhip_index {

@@ -437,5 +437,8 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
 #include "cluster.hpp"
 
+// SACSegmentation (planes): batched RANSAC scoring, one pass over the points per batch of hypotheses
+#include "sac.hpp"
+
 // SampleConsensusPrerejective: its scoring pass is a bounded 1-NN traversal of the target index
 #include "scp.hpp"
