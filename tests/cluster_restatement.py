@@ -4,7 +4,8 @@ over radiusSearch lists with the library's float32 d2 = (dx*dx + dy*dy) + dz*dz 
 The lists come from a uniform grid of cells no smaller than r (every neighbour lies in the 27 cells around a point), so
 50,000 points take seconds.  The reference leaves the order of clusters of equal size to an unstable std::sort; this
 project's rule is applied instead: size descending, ties by ascending smallest index.  Deviation restated as well: a
-non-finite record belongs to no cluster."""
+non-finite record belongs to no cluster.  A record that `indices` names more than once is in its cluster once, as the
+reference's processed[] has it."""
 import numpy as np
 
 UINT32_MAX = 2 ** 32 - 1
@@ -115,7 +116,11 @@ def euclidean_clusters(cloud, tolerance, min_size=1, max_size=UINT32_MAX, indice
     """-> (clusters: list of ascending int32 arrays of original ids, labels (n,) int32, n_clustered)"""
     cloud = np.asarray(cloud, np.float32)[:, :3]
     n = len(cloud)
-    ids = np.arange(n, dtype=np.int64) if indices is None else np.asarray(indices, np.int64)
+    ids = np.arange(n, dtype=np.int64) if indices is None else np.asarray(indices, np.int64).reshape(-1)
+    # the flood marks records (processed[], :157-191): a record the list names again is in its cluster once and counts
+    # once.  The first mention stands for it; the later ones find it processed.
+    if len(ids):
+        ids = ids[np.sort(np.unique(ids, return_index=True)[1])]
     p = cloud[ids]
     if scale is not None:
         p = p * np.asarray(scale, np.float32)[None, :]
@@ -230,3 +235,85 @@ def blob_cloud(kmax=40, seed=8):
 
 def random_volume(n=50000, seed=9):
     return np.random.default_rng(seed).random((n, 3), dtype=np.float32)
+
+
+def repeated_index_lists(n=397, seed=10):
+    """index lists over n records that name records again -> (base without repeats, {name: list}): the base followed by
+    its first ten entries, every entry twice in a row, and a shuffle of the base with every third entry once more"""
+    base = np.arange(0, n, 2, dtype=np.int32)
+    rng = np.random.default_rng(seed)
+    mixed = np.concatenate([base, base[::3]])
+    return base, {"head_again": np.concatenate([base, base[:10]]), "each_twice": np.repeat(base, 2),
+                  "permuted": mixed[rng.permutation(len(mixed))].astype(np.int32)}
+
+
+def pairs_cloud(k, lone=300, seed=11):
+    """k pairs at x = 10 i and 10 i + 0.5 and `lone` single points (x = 10 (k + j), y = 5), shuffled -> (cloud, pair of
+    every record or -1).  At tolerance 0.75 the components are the pairs and the lone points."""
+    c = np.zeros((2 * k + lone, 3), np.float32)
+    c[0:2 * k:2, 0] = 10.0 * np.arange(k)
+    c[1:2 * k:2, 0] = 10.0 * np.arange(k) + 0.5
+    c[2 * k:, 0] = 10.0 * (k + np.arange(lone))
+    c[2 * k:, 1] = 5.0
+    pair = np.concatenate([np.repeat(np.arange(k), 2), np.full(lone, -1)])
+    assert 10.0 * (k + lone) < 2.0 ** 22  # every x is exact in float32
+    p = np.random.default_rng(seed).permutation(len(c))
+    return c[p], pair[p]
+
+
+def striped_lattice(bands, width=1024, seed=12):
+    """integer (x, y, 0): band b is the rows y = 4 b, 4 b + 1, 4 b + 2 (row 4 b + 3 is absent) over the columns
+    0 .. width - 1 - 7 (b mod 5), shuffled -> (cloud, band of every record).  Rows of a band are 1 apart, bands 2 apart."""
+    xs, ys = [], []
+    for b in range(bands):
+        w = width - 7 * (b % 5)
+        for row in range(3):
+            xs.append(np.arange(w, dtype=np.float32))
+            ys.append(np.full(w, 4 * b + row, np.float32))
+    c = np.zeros((sum(len(x) for x in xs), 3), np.float32)
+    c[:, 0], c[:, 1] = np.concatenate(xs), np.concatenate(ys)
+    c = c[np.random.default_rng(seed).permutation(len(c))]
+    return c, (c[:, 1].astype(np.int64) // 4)
+
+
+def lattice_bands_for(points, width=1024):
+    """the smallest number of bands of striped_lattice(width=width) that holds at least `points` records"""
+    per5 = 3 * sum(width - 7 * r for r in range(5))
+    bands = 5 * (points // per5)
+    have = (bands // 5) * per5
+    while have < points:
+        have += 3 * (width - 7 * (bands % 5))
+        bands += 1
+    return bands
+
+
+def triple_cloud(n=5000, seed=13):
+    """n copies of each of (0,0,0), (1,0,0), (2,0,0), shuffled -> (cloud, which point)"""
+    c = np.zeros((3 * n, 3), np.float32)
+    which = np.repeat(np.arange(3), n)
+    c[:, 0] = which
+    p = np.random.default_rng(seed).permutation(3 * n)
+    return c[p], which[p]
+
+
+def clusters_of_groups(group, min_size=1, max_size=UINT32_MAX):
+    """the closed form: records with the same group >= 0 are one component (group < 0: a component of its own) ->
+    (clusters, labels, n_clustered) as euclidean_clusters returns them, from sorting alone"""
+    group = np.asarray(group, np.int64)
+    n = len(group)
+    g = group.copy()
+    alone = np.nonzero(g < 0)[0]
+    g[alone] = (g.max() + 1 if n else 0) + np.arange(len(alone))
+    order = np.argsort(g, kind="stable")  # ascending ids inside every group
+    starts = np.nonzero(np.r_[True, g[order][1:] != g[order][:-1]])[0] if n else np.empty(0, np.int64)
+    ends = np.r_[starts[1:], n]
+    size = ends - starts
+    keep = (size >= min_size) & (size <= max_size)
+    starts, ends, size = starts[keep], ends[keep], size[keep]
+    first = order[starts]
+    rank = np.lexsort((first, -size))
+    clusters = [order[starts[r]:ends[r]].astype(np.int32) for r in rank]
+    labels = np.full(n, -1, np.int32)
+    for r, c in enumerate(clusters):
+        labels[c] = r
+    return clusters, labels, int(size.sum())

@@ -103,3 +103,56 @@ def test_restatement_on_closed_forms():
     cloud, row = cr.two_rows(64, gap_axis=2)
     assert sizes(cr.euclidean_clusters(cloud, cr.JUST_ABOVE_ONE)[0]) == [64, 64]
     assert sizes(cr.euclidean_clusters(cloud, cr.JUST_ABOVE_ONE, scale=(1, 1, 0))[0]) == [128]
+
+
+def test_restatement_on_repeated_indices():
+    """a record named more than once is in its cluster once: against brute force over the distinct records of bun0"""
+    b = np.ascontiguousarray(np.load(os.path.join(GOLD, "bunny.npz"))["bun0"][:, :3], np.float32)
+    base, lists = cr.repeated_index_lists(len(b))
+    assert len(base) == 199 and len(lists["head_again"]) == 209 and len(lists["each_twice"]) == 398
+    assert len(np.unique(lists["permuted"])) == 199 and len(lists["permuted"]) > 199
+    assert not np.array_equal(lists["permuted"], np.sort(lists["permuted"]))
+    brute = [base[c] for c in cr.components_bruteforce(b[base], 0.01)]
+    assert sizes(brute)[:3] == [21, 18, 12]
+    plain = cr.euclidean_clusters(b, 0.01, indices=base)
+    assert same(plain[0], brute) and plain[2] == 199
+    for name, ind in lists.items():
+        c, lab, nc = cr.euclidean_clusters(b, 0.01, indices=ind)
+        assert same(c, brute), name
+        assert nc == 199 and np.array_equal(lab, plain[1]), name
+        cat = np.concatenate(c)
+        assert len(np.unique(cat)) == len(cat) == 199 and np.isin(cat, base).all(), name
+        # the size range counts distinct records
+        c, lab, nc = cr.euclidean_clusters(b, 0.01, 13, 20, indices=ind)
+        assert sizes(c) == [s for s in sizes(brute) if 13 <= s <= 20] and same(c, [x for x in brute if 13 <= len(x) <= 20])
+
+
+def test_closed_forms_of_the_regime_clouds():
+    """the clouds of tests/test_gpu_cluster_regimes.py at small sizes: the closed form (clusters_of_groups over the group
+    the coordinates give) is what the flood gives"""
+    def agree(ref, got):
+        assert same(ref[0], got[0]) and np.array_equal(ref[1], got[1]) and ref[2] == got[2]
+
+    chain = cr.integer_chain(300)
+    agree(cr.clusters_of_groups(np.full(300, -1)), cr.euclidean_clusters(chain, 0.5))
+    assert np.array_equal(cr.clusters_of_groups(np.full(300, -1))[1], np.arange(300))
+    for k in (1, 7, 40):
+        cloud, pair = cr.pairs_cloud(k, lone=9)
+        ref = cr.clusters_of_groups(pair, 2)
+        agree(ref, cr.euclidean_clusters(cloud, 0.75, 2))
+        assert sizes(ref[0]) == [2] * k and (ref[1][pair < 0] == -1).all() and ref[2] == 2 * k
+        firsts = [int(c[0]) for c in ref[0]]
+        assert firsts == sorted(firsts)
+    bands = cr.lattice_bands_for(1500, width=40)
+    cloud, band = cr.striped_lattice(bands, width=40)
+    assert len(cloud) >= 1500 and len(cr.striped_lattice(bands - 1, width=40)[0]) < 1500 and bands > 10
+    for tol in (cr.JUST_ABOVE_ONE, 2.0):
+        ref = cr.clusters_of_groups(band)
+        agree(ref, cr.euclidean_clusters(cloud, tol))
+        assert len(set(sizes(ref[0]))) == 5 and len(ref[0]) == bands
+    one = cr.euclidean_clusters(cloud, float(np.nextafter(np.float32(2), np.float32(3))))
+    agree(cr.clusters_of_groups(np.zeros(len(cloud), np.int64)), one)
+    assert sizes(one[0]) == [len(cloud)]
+    cloud, which = cr.triple_cloud(40)
+    agree(cr.clusters_of_groups(which), cr.euclidean_clusters(cloud, 0.5))
+    agree(cr.clusters_of_groups(np.zeros(120, np.int64)), cr.euclidean_clusters(cloud, cr.JUST_ABOVE_ONE))

@@ -25,11 +25,22 @@ def wavesim_lib():
     return os.path.join(WS, "libpclhip_wavesim.so")
 
 
-def test_cluster_gpu_tests_on_the_emulation(wavesim_lib):
+def on_the_emulation(wavesim_lib, module, select):
     env = dict(os.environ, PCLHIP_LIB=wavesim_lib, PCLHIP_ALLOW_WAVESIM="1")
-    cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", GPU_ONLY,
-           os.path.join(ROOT, "tests", "test_gpu_cluster.py")]
+    cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", select,
+           os.path.join(ROOT, "tests", module)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
     tail = r.stdout[-3000:] + "\n" + r.stderr[-3000:]
     assert r.returncode == 0, tail
     assert " passed" in r.stdout and " failed" not in r.stdout and " skipped" not in r.stdout, tail
+
+
+def test_cluster_gpu_tests_on_the_emulation(wavesim_lib):
+    on_the_emulation(wavesim_lib, "test_gpu_cluster.py", GPU_ONLY)
+
+
+def test_cluster_regimes_on_the_emulation(wavesim_lib):
+    """tests/test_gpu_cluster_regimes.py: the `fullgrid` cases stay on the GPU as well -- their sizes follow the device's
+    CU count, and with its 32 blocks the emulation reaches the hook kernel's second query group at the sizes of the module
+    above already"""
+    on_the_emulation(wavesim_lib, "test_gpu_cluster_regimes.py", GPU_ONLY + " and not fullgrid")

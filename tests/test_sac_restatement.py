@@ -92,3 +92,21 @@ def test_non_finite_sample_counts_zero_and_is_no_skip(cloud):
     assert not skipped and not np.isfinite(c).all()
     assert sac.count_within(cloud, c, 0.03) == 0
     assert sac.count_within(cloud, [0, 0, 1, np.inf], 0.03) == 0 and sac.count_within(cloud, [0, 0, 1, 0], 0.0) == 0
+
+
+def test_unstable_flags_every_trial_far_from_the_origin():
+    """The reading behind the instability cap of 0 in tests/test_gpu_sac_regimes.py: on the cloud shifted by
+    (1000, -2000, 500) `unstable` flags EVERY scored trial (with |a x| + |b y| + |c z| + |d| in the thousands some point
+    always lies within 4 * 2^-24 of that from the threshold), so there is no seed to change to and nothing to exclude: the
+    device has to meet all of them bit for bit, which is what that module asserts.  On the unshifted scene it flags none
+    of the trials here."""
+    from test_gpu_sac import scene
+    cloud = (scene(5000, seed=4).astype(np.float64) + np.array([1000.0, -2000.0, 500.0])).astype(np.float32)
+    ref = sac.segment(cloud, 0.012, seed=2, optimize=False)
+    assert (ref["trials"], ref["skipped"], ref["best_count"]) == (14, 0, 3319)
+    assert all(sac.unstable(cloud, t["coefficients"], 0.012) for t in ref["trace"])
+    near = scene(5000, seed=4)
+    ref = sac.segment(near, 0.012, seed=2, optimize=False)
+    flagged = sum(sac.unstable(near, t["coefficients"], 0.012) for t in ref["trace"] if not t["skipped"])
+    print("unshifted: %d of %d trials flagged" % (flagged, ref["trials"]))
+    assert flagged == 0

@@ -6,9 +6,10 @@ the blocks' adds to count[h] really interleave here."""
 import os
 import shutil
 import subprocess
-import sys
 
 import pytest
+
+from test_cluster_wavesim import on_the_emulation
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WS = os.path.join(ROOT, "tests", "wavesim")
@@ -26,10 +27,11 @@ def wavesim_lib():
 
 
 def test_sac_gpu_tests_on_the_emulation(wavesim_lib):
-    env = dict(os.environ, PCLHIP_LIB=wavesim_lib, PCLHIP_ALLOW_WAVESIM="1")
-    cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", GPU_ONLY,
-           os.path.join(ROOT, "tests", "test_gpu_sac.py")]
-    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
-    tail = r.stdout[-3000:] + "\n" + r.stderr[-3000:]
-    assert r.returncode == 0, tail
-    assert " passed" in r.stdout and " failed" not in r.stdout and " skipped" not in r.stdout, tail
+    on_the_emulation(wavesim_lib, "test_gpu_sac.py", GPU_ONLY)
+
+
+def test_sac_regimes_on_the_emulation(wavesim_lib):
+    """tests/test_gpu_sac_regimes.py: the `fullgrid` cases stay on the GPU as well -- their sizes follow the device's CU
+    count, and with its 32 blocks the emulation reaches the scoring kernel's second tile at the sizes of the module above
+    already"""
+    on_the_emulation(wavesim_lib, "test_gpu_sac_regimes.py", GPU_ONLY + " and not fullgrid")
