@@ -82,6 +82,9 @@ PCLHIP_API pclhip_status pclhip_ctx_reserve(pclhip_ctx* ctx, uint64_t bytes);
  *   "served_groups"  0 | 1  target sharding: pclhip_icp_align / pclhip_icp_run_steps walk only the 64-point groups the rank
  *                           serves (default 1; 0 = every launch walks the whole source -- the reference of the tests)
  *   "icp_lookahead"  n      pclhip_icp_align: iterations queued ahead of the host's knowledge (default 1)
+ *   "step_events"    0 | 1  1: the chain-free device-driven loop brackets the kernels of a step with HIP events, like the
+ *                           loops with rejectors / reciprocal / served groups / per-lane search do (default 0: its kernels
+ *                           stamp their own times and the step record is the completion signal; an A/B switch)
  *   "cache_mb"       n      device blocks kept for reuse between calls, MiB (default 16384, at most a quarter of the device)
  *   "arena_mb"       n      size of the automatic arena (pclhip_ctx_reserve), MiB; 0 = none (default: 288 B per point);
  *                           PCLHIP_ERR_STATE once the arena exists
@@ -505,9 +508,15 @@ typedef struct {
   int alignment_ended;        /* this step was the last of its alignment */
   uint64_t num_correspondences;
   double mse;
-  float search_ms;            /* HIP events on the context's stream: the search kernel ... */
-  float kernels_ms;           /* ... search + accumulation ... */
-  float step_ms;              /* ... the whole step incl. reduction, (all-reduce,) solve */
+  /* Three intervals from one start: the moment the previous step's closing kernel was done (the first step of a call: the
+   * upload of the control block).  The chain-free loop (no rejectors, no reciprocal test, no served groups, no per-lane
+   * search) takes them from stamps of the device's constant-rate counter that the step's own kernels leave: the start is
+   * the exit stamp of the previous closing kernel, and each end is the entry of the NEXT kernel, so each interval includes
+   * one launch latency.  Every other loop, and the chain-free one under option "step_events", brackets the kernels with
+   * HIP events on the context's stream: the same bounds, plus the events' own cost. */
+  float search_ms;            /* start .. the search launch is done (the accumulation kernel starts) */
+  float kernels_ms;           /* start .. search + accumulation are done (the reduction kernel starts) */
+  float step_ms;              /* start .. the whole step incl. reduction, (all-reduce,) solve (the closing kernel's exit) */
   float final_transformation[16];
 } pclhip_icp_step;
 PCLHIP_API pclhip_status pclhip_icp_run_steps(pclhip_icp* icp, const pclhip_icp_params* params,

@@ -73,7 +73,7 @@ class Context:
         check(self.lib.pclhip_ctx_reserve(self.h, int(nbytes)), self.h)
 
     def setOption(self, name, value):
-        """pclhip_ctx_set_option: "served_groups", "icp_lookahead", "cache_mb", "arena_mb", "lane_search", "lane_max_up",
+        """pclhip_ctx_set_option: "served_groups", "icp_lookahead", "step_events", "cache_mb", "arena_mb", "lane_search", "lane_max_up",
         "lane_far" (none changes a result)."""
         check(self.lib.pclhip_ctx_set_option(self.h, name.encode(), float(value)), self.h)
 

@@ -144,24 +144,26 @@ void dev_reserve_for_points(pclhip_ctx* ctx, uint64_t points) {
   if (want > 0) (void)reserve_arena(ctx, want);
 }
 
-hipError_t pinned_malloc(pclhip_ctx* ctx, void** p, size_t bytes) {
+hipError_t pinned_malloc(pclhip_ctx* ctx, void** p, size_t bytes, bool coherent) {
   {
     std::lock_guard<std::mutex> lock(ctx->cache_mutex);
-    for (size_t i = 0; i < ctx->pinned_cache.size(); ++i)
-      if (ctx->pinned_cache[i].second == bytes) {
-        *p = ctx->pinned_cache[i].first;
-        ctx->pinned_cache.erase(ctx->pinned_cache.begin() + long(i));
+    auto& cache = coherent ? ctx->pinned_cache_coherent : ctx->pinned_cache;
+    for (size_t i = 0; i < cache.size(); ++i)
+      if (cache[i].second == bytes) {
+        *p = cache[i].first;
+        cache.erase(cache.begin() + long(i));
         return hipSuccess;
       }
   }
-  return hipHostMalloc(p, bytes, hipHostMallocDefault);
+  return hipHostMalloc(p, bytes, coherent ? hipHostMallocCoherent : hipHostMallocDefault);
 }
 
-void pinned_free(pclhip_ctx* ctx, void* p, size_t bytes) {
+void pinned_free(pclhip_ctx* ctx, void* p, size_t bytes, bool coherent) {
   if (!p) return;
   std::lock_guard<std::mutex> lock(ctx->cache_mutex);
-  if (ctx->pinned_cache.size() < 64 && bytes <= (size_t(1) << 20)) {
-    ctx->pinned_cache.emplace_back(p, bytes);
+  auto& cache = coherent ? ctx->pinned_cache_coherent : ctx->pinned_cache;
+  if (cache.size() < 64 && bytes <= (size_t(1) << 20)) {
+    cache.emplace_back(p, bytes);
     return;
   }
   (void)hipHostFree(p);
@@ -541,6 +543,8 @@ pclhip_status pclhip_ctx_set_option(pclhip_ctx* ctx, const char* name, double va
     ctx->opt_served_groups = value != 0.0 ? 1 : 0;
   } else if (!std::strcmp(name, "icp_lookahead")) {
     ctx->opt_lookahead = value > 62.0 ? 62 : int(value);  // the step ring holds 64 records (icp_loop.hip)
+  } else if (!std::strcmp(name, "step_events")) {
+    ctx->opt_step_events = value != 0.0 ? 1 : 0;
   } else if (!std::strcmp(name, "cache_mb")) {
     size_t limit = size_t(value) << 20;
     size_t free_b = 0, total_b = 0;
@@ -569,7 +573,7 @@ pclhip_status pclhip_ctx_set_option(pclhip_ctx* ctx, const char* name, double va
   } else if (!std::strcmp(name, "lane_far")) {
     ctx->opt_lane_far = float(value);
   } else {
-    pclhip::set_error(ctx, "unknown option (served_groups, icp_lookahead, cache_mb, arena_mb, cell_start, reseed, lane_search, lane_max_up, lane_far)");
+    pclhip::set_error(ctx, "unknown option (served_groups, icp_lookahead, step_events, cache_mb, arena_mb, cell_start, reseed, lane_search, lane_max_up, lane_far)");
     return PCLHIP_ERR_INVALID;
   }
   return PCLHIP_OK;
@@ -586,6 +590,8 @@ void pclhip_ctx_destroy(pclhip_ctx* ctx) {
   dev_cache_release(ctx);
   for (auto& b : ctx->pinned_cache) (void)hipHostFree(b.first);
   ctx->pinned_cache.clear();
+  for (auto& b : ctx->pinned_cache_coherent) (void)hipHostFree(b.first);
+  ctx->pinned_cache_coherent.clear();
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1497,7 +1503,8 @@ void pclhip_icp_destroy(pclhip_icp* icp) {
   if (icp->rej_state_host) pinned_free(icp->ctx, icp->rej_state_host, sizeof(pclhip::RejState));
   if (icp->ctl) (void)dev_free(icp->ctx, icp->ctl);
   if (icp->ctl_host) pinned_free(icp->ctx, icp->ctl_host, sizeof(pclhip::IcpControl));
-  if (icp->steps) pinned_free(icp->ctx, icp->steps, sizeof(pclhip::IcpStepRecord) * size_t(icp->steps_capacity));
+  if (icp->steps) pinned_free(icp->ctx, icp->steps, sizeof(pclhip::IcpStepRecord) * size_t(icp->steps_capacity), true);
+  if (icp->step_stamps) (void)dev_free(icp->ctx, icp->step_stamps);
   for (hipEvent_t e : icp->step_events)
     if (e) (void)hipEventDestroy(e);
   if (icp->ev0) (void)hipEventDestroy(icp->ev0);

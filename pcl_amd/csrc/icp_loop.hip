@@ -9,6 +9,12 @@
 // one after a finished alignment falls through (`stop`), and the host only reads the step records the solve
 // kernel leaves in pinned memory -- one iteration behind the GPU, so it never stalls it.
 //
+// A step comes in two kinds.  The chain-free loop (no rejectors, no reciprocal test, no served-group lists, no per-lane
+// search) queues its kernels and nothing else: they stamp their own times (pclhip_step_clock.hpp), the closing kernel
+// copies the stamps into the step record and writes the record's sequence word last, and the host polls that word in
+// host-coherent memory.  Every other loop -- and the chain-free one under option "step_events" -- brackets the kernels of a
+// step with four events, as all of them once did; the events of a registration are made when the first such step is queued.
+//
 // Multi-GPU: the 32-double record is summed over the ranks between the reduction and the solve, on the same
 // stream -- ncclAllReduce through a communicator created here (RCCL over xGMI), or the caller's hook.
 #include <hip/hip_runtime.h>
@@ -22,7 +28,10 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <sched.h>
+
 #include "pclhip_internal.hpp"
+#include <pclhip_step_clock.hpp>  // the stamps' rate and the stream query: through the include path, like search.hip
 #include "rccl_abi.hpp"  // the by-value constants of RCCL's ABI; checked against <rccl/rccl.h> by rccl_abi_check.cpp
 
 using namespace pclhip;
@@ -305,23 +314,40 @@ bool icp_is_sharded(const pclhip_icp* icp) { return icp->comm != nullptr || icp-
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int kRing = 64;  // step records / event quadruples in flight at most
+constexpr int kRing = 64;  // step records in flight at most
 
 pclhip_status ensure_loop_state(pclhip_icp* icp) {
   pclhip_ctx* ctx = icp->ctx;
   if (icp->ctl != nullptr) return PCLHIP_OK;
-  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->ctl, sizeof(IcpControl)));
-  PCLHIP_CHECK_HIP(ctx, pinned_malloc(ctx, &icp->ctl_host, sizeof(IcpControl)));
-  PCLHIP_CHECK_HIP(ctx, pinned_malloc(ctx, &icp->steps, sizeof(IcpStepRecord) * kRing));
+  if (ctx->step_clock_khz == 0) {  // once per context
+    int khz = 0;
+    PCLHIP_CHECK_HIP(ctx, step_clock_rate_khz(ctx->device, &khz));
+    if (khz <= 0) {
+      set_error(ctx, "the device reports no wall clock rate");
+      return PCLHIP_ERR_STATE;
+    }
+    ctx->step_clock_khz = khz;
+  }
+  // the ring is polled by the host while the closing kernels write it: explicitly host-coherent, nothing flushes for it
+  PCLHIP_CHECK_HIP(ctx, pinned_malloc(ctx, &icp->steps, sizeof(IcpStepRecord) * kRing, true));
   std::memset(icp->steps, 0, sizeof(IcpStepRecord) * kRing);
   icp->steps_capacity = kRing;
-  icp->step_events.assign(size_t(kRing) * 4, nullptr);
-  for (int i = 0; i < kRing; ++i) {
-    // markers between kernels of one stream: device-scope release is enough; the last one of a step
-    // publishes the step record to the host, so it releases to the system
-    for (int e = 0; e < 4; ++e)
-      PCLHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&icp->step_events[size_t(i) * 4 + e],
-                                                    e == 3 ? hipEventDefault : hipEventReleaseToDevice));
+  icp->step_marked.assign(size_t(kRing), 0);
+  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->step_stamps, STAMP_WORDS * sizeof(unsigned long long)));
+  PCLHIP_CHECK_HIP(ctx, pinned_malloc(ctx, &icp->ctl_host, sizeof(IcpControl)));
+  PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &icp->ctl, sizeof(IcpControl)));  // (last: its presence says the state is complete)
+  return PCLHIP_OK;
+}
+
+// The events of `count` steps of the event kind in flight (4 each), made the first time they are needed: markers between
+// kernels of one stream, for which a device-scope release is enough; the last one of a step is the one the host waits on
+// before it reads the step record, so it releases to the system.
+pclhip_status ensure_step_events(pclhip_icp* icp, int count) {
+  pclhip_ctx* ctx = icp->ctx;
+  while (icp->step_events.size() < size_t(count) * 4) {
+    hipEvent_t e = nullptr;
+    PCLHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&e, icp->step_events.size() % 4 == 3 ? hipEventDefault : hipEventReleaseToDevice));
+    icp->step_events.push_back(e);
   }
   return PCLHIP_OK;
 }
@@ -369,8 +395,37 @@ pclhip_status arm_loop(pclhip_icp* icp, const pclhip_icp_params* p, const float*
     c.st.iterations_similar_transforms = icp->iterations_similar_transforms;
     c.st.convergence_state = icp->convergence_state;
   }
+  // no record of an earlier loop is taken for one of this loop (the stream is idle: nobody writes the ring now)
+  for (int i = 0; i < icp->steps_capacity; ++i) icp->steps[i].seq = 0u;
   PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(icp->ctl, icp->ctl_host, sizeof c, hipMemcpyHostToDevice, ctx->stream));
+  // the marker-free loop: its first step starts when the upload is done (once per call; later steps start at their
+  // predecessor's exit stamp)
+  if (!icp_step_needs_events(icp, p->mode)) return launch_step_start_stamp(icp);
   return PCLHIP_OK;
+}
+
+// Waits until the closing kernel of step `step` has published its record in `slot`: spins on the sequence word, gives
+// the core away after a bounded number of spins, and asks the stream every few thousand polls so that the wait cannot
+// hang -- a failed stream returns its error, and a stream that is done without the record being there (one more look:
+// the stream may have finished between the poll and the query) is an error of the loop.
+pclhip_status wait_step_record(pclhip_icp* icp, const IcpStepRecord* slot, long step) {
+  pclhip_ctx* ctx = icp->ctx;
+  const unsigned want = unsigned(step) + 1u;
+  constexpr unsigned kSpinsBeforeYield = 256, kPollsPerQuery = 4096;
+  for (unsigned polls = 1;; ++polls) {
+    if (__atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) == want) return PCLHIP_OK;
+    if (polls % kPollsPerQuery == 0) {
+      const hipError_t q = step_stream_query(ctx->stream);
+      if (q == hipSuccess) {
+        if (__atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) == want) return PCLHIP_OK;
+        set_error(ctx, "ICP loop: step record missing");
+        return PCLHIP_ERR_STATE;
+      }
+      if (q != hipErrorNotReady) PCLHIP_CHECK_HIP(ctx, q);
+    } else if (polls > kSpinsBeforeYield) {
+      sched_yield();
+    }
+  }
 }
 
 struct StepTimes {
@@ -394,10 +449,18 @@ pclhip_status run_loop(pclhip_icp* icp, const pclhip_icp_params* p, int window, 
   long enq = 0, done = 0;
   bool feed = true;
   pclhip_status st = PCLHIP_OK;
+  // which kind the steps of this loop are (one flag per queued step: step_marked)
+  const bool marked = icp_step_needs_events(icp, p->mode);
+  if (marked) {  // no more events than the window can have in flight
+    st = ensure_step_events(icp, window);
+    if (st != PCLHIP_OK) return st;
+  }
+  const double ms_per_tick = 1.0 / double(ctx->step_clock_khz);
   while (done < enq || (feed && (max_steps < 0 || enq < max_steps))) {
     while (feed && (max_steps < 0 || enq < max_steps) && enq - done < window) {
-      hipEvent_t* ev = &icp->step_events[size_t(enq % icp->steps_capacity) * 4];
-      st = launch_icp_iterate(icp, nullptr, fmax2, use_max, p->mode, ev);
+      icp->step_marked[size_t(enq % icp->steps_capacity)] = marked ? 1 : 0;
+      st = launch_icp_iterate(icp, nullptr, fmax2, use_max, p->mode, marked ? ICP_STEP_DEVICE_EVENTS : ICP_STEP_DEVICE_STAMPED,
+                              marked ? &icp->step_events[size_t(enq % window) * 4] : nullptr);
       if (st != PCLHIP_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return st;
@@ -405,21 +468,42 @@ pclhip_status run_loop(pclhip_icp* icp, const pclhip_icp_params* p, int window, 
       ++enq;
     }
     if (done == enq) break;
-    hipEvent_t* ev = &icp->step_events[size_t(done % icp->steps_capacity) * 4];
-    PCLHIP_CHECK_HIP(ctx, hipEventSynchronize(ev[3]));
-    const IcpStepRecord rec = icp->steps[done % icp->steps_capacity];
-    StepTimes t;
-    if (feed) {  // launches queued behind a finished alignment fell through: no record, no times
-      if (rec.step != int(done)) {
-        set_error(ctx, "ICP loop: step record out of sequence");
+    // launches queued behind a finished alignment fall through and write no record: nothing to wait for per step (the
+    // callers close with a hipStreamSynchronize)
+    if (!feed) {
+      done = enq;
+      break;
+    }
+    const IcpStepRecord* slot = &icp->steps[done % icp->steps_capacity];
+    const bool by_event = icp->step_marked[size_t(done % icp->steps_capacity)] != 0;
+    hipEvent_t* ev = by_event ? &icp->step_events[size_t(done % window) * 4] : nullptr;
+    if (by_event) {
+      PCLHIP_CHECK_HIP(ctx, hipEventSynchronize(ev[3]));
+    } else {
+      st = wait_step_record(icp, slot, done);
+      if (st != PCLHIP_OK) {
         (void)hipStreamSynchronize(ctx->stream);
-        return PCLHIP_ERR_STATE;
+        return st;
       }
+    }
+    const IcpStepRecord rec = *slot;
+    if (rec.step != int(done) || rec.seq != unsigned(done) + 1u) {
+      set_error(ctx, "ICP loop: step record out of sequence");
+      (void)hipStreamSynchronize(ctx->stream);
+      return PCLHIP_ERR_STATE;
+    }
+    StepTimes t;
+    if (by_event) {
       (void)hipEventElapsedTime(&t.search_ms, ev[0], ev[1]);
       (void)hipEventElapsedTime(&t.kernels_ms, ev[0], ev[2]);
       (void)hipEventElapsedTime(&t.step_ms, ev[0], ev[3]);
-      if (!on_step(rec, t)) feed = false;
+    } else {
+      const unsigned long long t0 = rec.stamp[STAMP_START];
+      t.search_ms = float(double(rec.stamp[STAMP_SEARCH_END] - t0) * ms_per_tick);
+      t.kernels_ms = float(double(rec.stamp[STAMP_KERNELS_END] - t0) * ms_per_tick);
+      t.step_ms = float(double(rec.stamp[STAMP_EXIT] - t0) * ms_per_tick);
     }
+    if (!on_step(rec, t)) feed = false;
     ++done;
   }
   return PCLHIP_OK;

@@ -179,7 +179,14 @@ struct RejState {
   double threshold;        // ... times the factor
 };
 
-// One record per completed iteration, written by icp_solve_kernel into pinned host memory.
+// The stamps of a step of the marker-free device-driven loop (pclhip_step_clock.hpp: ticks of the constant-rate counter),
+// in a small device block of the registration: the step's kernels leave theirs here, the kernel that closes the step
+// copies the four into the step record and leaves its exit stamp as the next step's start.
+enum { STAMP_START = 0, STAMP_SEARCH_END = 1, STAMP_KERNELS_END = 2, STAMP_EXIT = 3, STAMP_WORDS = 4 };
+
+// One record per completed iteration, written by the kernel that closes it (icp_solve_step) into host-coherent pinned
+// memory.  `seq` is written LAST (payload, __threadfence_system(), system-scope release store of step + 1): the host
+// that reads step + 1 there with an acquire load may read the payload.  0 = empty (arm_loop clears the ring's words).
 struct IcpStepRecord {
   int step;               // running index
   int iteration;          // nr_iterations_ after this iteration (0: it failed for lack of correspondences)
@@ -192,6 +199,9 @@ struct IcpStepRecord {
   double prev_mse;        // criteria memory after this iteration
   float Tk[16];           // transformation_ of this iteration
   float final_T[16];      // final_transformation_ after it
+  unsigned long long stamp[STAMP_WORDS];  // marker-free steps: start, search end, kernels end, exit (zeros otherwise)
+  unsigned int seq;       // step + 1, the completion signal
+  unsigned int pad;
 };
 
 }  // namespace pclhip
@@ -225,6 +235,8 @@ struct pclhip_ctx {
   // pclhip_ctx_set_option (none of them changes a result)
   int opt_served_groups = 1;            // target sharding: the device-driven loop walks the served groups only
   int opt_lookahead = 1;                // pclhip_icp_align: iterations queued ahead of the host's knowledge
+  int opt_step_events = 0;              // 1: the chain-free device-driven loop brackets its kernels with events too (A/B)
+  int step_clock_khz = 0;               // rate of the step stamps' counter, read once (icp_loop.hip: ensure_loop_state)
   long long opt_arena_mb = -1;          // automatic arena: -1 = 288 B per point of the first large cloud, 0 = none
   int opt_lane_search = 0;              // 1: seeded ICP launches one lane per query (lane.hip) -- exact, measured 2.5x SLOWER than the
                                         // wave-cooperative body at 10M points (profiles/r05_lane_search_ab.txt): kept as a tested option
@@ -244,6 +256,7 @@ struct pclhip_ctx {
   // Small pinned host blocks (control blocks, step rings, mirrored states of the registrations) are kept for the
   // context's lifetime: hipHostFree synchronises the device (170 us each, three per registration object).
   std::vector<std::pair<void*, size_t>> pinned_cache;  // free blocks (pointer, bytes)
+  std::vector<std::pair<void*, size_t>> pinned_cache_coherent;  // ... of those asked for with hipHostMallocCoherent
   // One reservation in front of that cache (pclhip_ctx_reserve; made automatically for the first cloud of a million
   // points or more): allocations are carved out of it (first fit, freed ranges coalesce), so a context's FIRST index
   // build pays one hipMalloc instead of some forty.  What does not fit goes the way above.
@@ -345,9 +358,12 @@ struct pclhip_icp {
   // device-driven loop (icp_loop.hip)
   pclhip::IcpControl* ctl = nullptr;        // device
   pclhip::IcpControl* ctl_host = nullptr;   // pinned staging copy used to arm the loop
-  pclhip::IcpStepRecord* steps = nullptr;   // pinned ring written by icp_solve_kernel
+  pclhip::IcpStepRecord* steps = nullptr;   // host-coherent pinned ring written by the kernel that closes a step
   int steps_capacity = 0;
-  std::vector<hipEvent_t> step_events;      // 4 per ring slot: start, after search, after accumulate, after solve
+  unsigned long long* step_stamps = nullptr;  // device, STAMP_WORDS: the stamps of the marker-free step under way
+  std::vector<hipEvent_t> step_events;      // steps of the event kind, 4 per step in flight (made on first use): start,
+                                            // after search, after accumulate, after solve
+  std::vector<uint8_t> step_marked;         // per ring slot: the step queued there is of the event kind
   pclhip_comm* comm = nullptr;              // native RCCL all-reduce of the record (dist.hip); not owned
   const pclhip_comm* target_size_checked_for = nullptr;  // check_same_target_size passed with this communicator
   pclhip::RegionBox region = {{0, 0, 0}, {0, 0, 0}, 0};  // target sharding: the source points this rank serves
@@ -381,11 +397,13 @@ namespace pclhip {
 // Frees device allocations and destroys events on scope exit (every early error return included).
 // context-cached device memory (api.hip): same contract as hipMalloc / hipFree
 hipError_t dev_malloc(pclhip_ctx* ctx, void** p, size_t bytes);
-hipError_t pinned_malloc(pclhip_ctx* ctx, void** p, size_t bytes);  // hipHostMalloc through the context's cache
-void pinned_free(pclhip_ctx* ctx, void* p, size_t bytes);
+// hipHostMalloc through the context's cache; coherent: explicitly host-coherent (hipHostMallocCoherent), for memory the
+// host polls while a kernel writes it
+hipError_t pinned_malloc(pclhip_ctx* ctx, void** p, size_t bytes, bool coherent = false);
+void pinned_free(pclhip_ctx* ctx, void* p, size_t bytes, bool coherent = false);
 template <class T>
-inline hipError_t pinned_malloc(pclhip_ctx* ctx, T** p, size_t bytes) {
-  return pinned_malloc(ctx, reinterpret_cast<void**>(p), bytes);
+inline hipError_t pinned_malloc(pclhip_ctx* ctx, T** p, size_t bytes, bool coherent = false) {
+  return pinned_malloc(ctx, reinterpret_cast<void**>(p), bytes, coherent);
 }
 void dev_free(pclhip_ctx* ctx, void* p);
 inline void dev_free_if(pclhip_ctx* ctx, void* p) {
@@ -592,8 +610,16 @@ struct NdtCells {
 pclhip_status ndt_build_cells(pclhip_ctx* ctx, const void* points, size_t stride, uint64_t n, float resolution,
                               uint32_t min_points_per_voxel, double min_covar_eigvalue_mult, NdtCells* cells);
 void ndt_free_cells(pclhip_ctx* ctx, NdtCells* cells);
+// The device-driven loop's step comes in two kinds (icp_loop.hip): DEVICE_EVENTS brackets its kernels with step_events[0..3],
+// DEVICE_STAMPED queues the kernels and nothing else -- they stamp their own times (icp->step_stamps) and the step record
+// is the completion signal.  The second serves the chain-free loop only: icp_step_needs_events says which.
+enum IcpStepKind { ICP_STEP_HOST = 0, ICP_STEP_DEVICE_EVENTS = 1, ICP_STEP_DEVICE_STAMPED = 2 };
 pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d2, bool use_max,
-                                 int mode, hipEvent_t* step_events = nullptr);
+                                 int mode, IcpStepKind kind = ICP_STEP_HOST, hipEvent_t* step_events = nullptr);
+// a rejector chain, the reciprocal test, served-group lists, the per-lane search or option "step_events": the event kind
+bool icp_step_needs_events(const pclhip_icp* icp, int mode);
+// the start stamp of the first marker-free step of a call: one thread, queued behind the control-block upload
+pclhip_status launch_step_start_stamp(pclhip_icp* icp);
 // target sharding, after a run of the device-driven loop: the working copies of the groups the last launches did not
 // serve are brought up to date (search.hip: served groups), stream-ordered
 pclhip_status owned_groups_catch_up(pclhip_icp* icp, int mode);

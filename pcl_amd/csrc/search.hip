@@ -18,6 +18,7 @@
 #include "normals_math.hpp"
 #include "device_scan.hpp"
 #include "icp_xform.hpp"
+#include <pclhip_step_clock.hpp>  // step_clock_now(): through the include path (the emulation of the test tier has its own)
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -1732,8 +1733,11 @@ __global__ __launch_bounds__(BLOCK) void icp_accumulate_kernel(IndexView ix, con
                                                                const IcpControl* __restrict__ ctl,
                                                                float4* __restrict__ src_nrm,
                                                                const float4* __restrict__ src_nrm0, int enforce,
-                                                               double* __restrict__ partials) {
+                                                               double* __restrict__ partials,
+                                                               unsigned long long* __restrict__ stamps = nullptr) {
   __shared__ double red_s[WAVES_PER_BLOCK][NS];
+  // a marker-free step of the device-driven loop: this kernel starts when the search launch in front of it is done
+  if (stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0) stamps[STAMP_SEARCH_END] = step_clock_now();
   bool restart = false;
   if (ctl != nullptr) {
     if (ctl->stop != 0) return;
@@ -1862,7 +1866,8 @@ __global__ __launch_bounds__(BLOCK) void estimate_pairs_kernel(const float4* __r
 // With `solve_ctl` the same launch also closes the iteration (icp_solve_step below): no record to exchange,
 // one launch less.
 __device__ __forceinline__ void icp_solve_step(IcpControl* __restrict__ ctl, const double* __restrict__ sums,
-                                               IcpStepRecord* __restrict__ log);
+                                               IcpStepRecord* __restrict__ log,
+                                               unsigned long long* __restrict__ stamps);
 
 // The thread that closes the iteration afterwards keeps the 6x6 system, the control block and the step record in
 // registers (94 of the 128 a 1024-thread block leaves per lane): icp_solve_step is inlined here -- as a called function
@@ -1873,11 +1878,14 @@ __global__ __launch_bounds__(FINALIZE_THREADS) void icp_finalize_kernel(const do
                                                                         const IcpControl* __restrict__ ctl = nullptr,
                                                                         IcpControl* __restrict__ solve_ctl = nullptr,
                                                                         IcpStepRecord* __restrict__ log = nullptr,
-                                                                        uint32_t* __restrict__ rearm_ctr = nullptr) {
+                                                                        uint32_t* __restrict__ rearm_ctr = nullptr,
+                                                                        unsigned long long* __restrict__ stamps = nullptr) {
   // the search launch of this iteration is through with the context's group counters: zero again for the next fed kernel
   // of the stream (PCLHIP_LAUNCH_REARM) -- also when the alignment has stopped, so the host need not know whether it has
   sched_ctr_rearm(rearm_ctr);
   if (ctl != nullptr && ctl->stop != 0) return;
+  // a marker-free step: the accumulation is done when this kernel starts (left in the block: the closing thread reads it there)
+  if (stamps != nullptr && threadIdx.x == 0) stamps[STAMP_KERNELS_END] = step_clock_now();
   __shared__ double red[32][NS + 1];
   __shared__ double total[NS];
   const int t = threadIdx.x % NS;  // NS == 32
@@ -1915,15 +1923,18 @@ __global__ __launch_bounds__(FINALIZE_THREADS) void icp_finalize_kernel(const do
   }
   if (solve_ctl != nullptr) {
     __syncthreads();
-    if (threadIdx.x == 0) icp_solve_step(solve_ctl, total, log);
+    if (threadIdx.x == 0) icp_solve_step(solve_ctl, total, log, stamps);
   }
 }
 
 // Closes an iteration on the device: closed form of the estimator on the (all-reduced) record, final = Tk *
 // final, DefaultConvergenceCriteria, and the control words of the next launch (impl/icp.hpp:204-238).
 // One thread: ~2k double operations, a few microseconds -- the point is that nothing leaves the GPU.
+// `stamps` (a marker-free step): the exit stamp is taken here, behind the solve and the control words, and left as the next
+// step's start -- what an event in front of the next search launch measured: this kernel is done.
 __device__ __forceinline__ void icp_solve_step(IcpControl* __restrict__ ctl, const double* __restrict__ sums,
-                                               IcpStepRecord* __restrict__ log) {
+                                               IcpStepRecord* __restrict__ log,
+                                               unsigned long long* __restrict__ stamps) {
   if (ctl->stop != 0) return;
   IcpControl c = *ctl;
   IcpStepRecord r;
@@ -1972,13 +1983,42 @@ __device__ __forceinline__ void icp_solve_step(IcpControl* __restrict__ ctl, con
   }
   ++c.step;
   *ctl = c;
-  log[r.step % c.log_capacity] = r;
-  __threadfence_system();
+#pragma unroll
+  for (int i = 0; i < STAMP_WORDS; ++i) r.stamp[i] = 0ull;
+  if (stamps != nullptr) {
+    const unsigned long long t_exit = step_clock_now();
+    r.stamp[STAMP_START] = stamps[STAMP_START];
+    r.stamp[STAMP_SEARCH_END] = stamps[STAMP_SEARCH_END];
+    r.stamp[STAMP_KERNELS_END] = stamps[STAMP_KERNELS_END];
+    r.stamp[STAMP_EXIT] = t_exit;
+    stamps[STAMP_START] = t_exit;
+  }
+  r.seq = 0u;
+  r.pad = 0u;
+  IcpStepRecord* __restrict__ slot = &log[r.step % c.log_capacity];
+  *slot = r;
+  // the completion signal, last: whoever reads step + 1 here (acquire) may read the payload
+  step_record_publish(&slot->seq, unsigned(r.step) + 1u);
 }
 
+// mid_stamps (a marker-free step whose source share is empty: no search, no accumulation, no reduction launch): the
+// search-end and kernels-end stamps are this kernel's entry.
 __global__ __launch_bounds__(64) void icp_solve_kernel(IcpControl* __restrict__ ctl, const double* __restrict__ sums,
-                                 IcpStepRecord* __restrict__ log) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) icp_solve_step(ctl, sums, log);
+                                 IcpStepRecord* __restrict__ log, unsigned long long* __restrict__ stamps,
+                                 int mid_stamps) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (stamps != nullptr && mid_stamps != 0 && ctl->stop == 0) {
+      const unsigned long long t = step_clock_now();
+      stamps[STAMP_SEARCH_END] = t;
+      stamps[STAMP_KERNELS_END] = t;
+    }
+    icp_solve_step(ctl, sums, log, stamps);
+  }
+}
+
+// The start stamp of the first marker-free step of a call (every later step starts at its predecessor's exit stamp).
+__global__ __launch_bounds__(64) void icp_step_start_stamp_kernel(unsigned long long* __restrict__ stamps) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) stamps[STAMP_START] = step_clock_now();
 }
 
 // flags of the search kernels: 1 a finite maximum distance is set, 2 seeded descents may start below the root
@@ -1989,10 +2029,10 @@ constexpr int SEARCH_RESTART_ONLY = 4;  // device-driven loop with the per-lane 
 
 template <int MODE>
 static void launch_accumulate(pclhip_icp* icp, const IndexView& v, int ga, const uint8_t* keep, const Mat34& M,
-                              const IcpControl* ctl, hipStream_t s) {
+                              const IcpControl* ctl, unsigned long long* stamps, hipStream_t s) {
   hipLaunchKernelGGL(icp_accumulate_kernel<MODE>, dim3(ga), dim3(BLOCK), 0, s, v, icp->src_cur, icp->n, icp->match_pos,
                      icp->match_d2, keep, M, ctl, icp->src_nrm_cur, icp->src_nrm_sorted0,
-                     icp->enforce_same_direction_normals ? 1 : 0, icp->partials);
+                     icp->enforce_same_direction_normals ? 1 : 0, icp->partials, stamps);
 }
 
 // Served-group lists (OwnedGroups): the arrays of a registration, made on first use; the boxes of the source's groups
@@ -2069,16 +2109,43 @@ static int sparse_source_shift(const pclhip_icp* icp) {
   return shift;
 }
 
-// One iteration.  ev == nullptr: the host-driven form (T by value, the caller reads the record back);
-// ev != nullptr: the device-driven form -- transform / restart / stop come from icp->ctl, the iteration is
-// closed by icp_solve_kernel, and ev[0..3] are recorded before the search, after it, after the accumulation
-// and after the solve.
+// The served-group lists and the per-lane search of a device-driven step, as launch_icp_iterate decides them
+static bool step_walks_served_groups(const pclhip_icp* icp, int mode) {
+  return icp->region.on != 0 && mode != PCLHIP_ICP_SYMMETRIC && icp->ctx->opt_served_groups != 0 && !icp->reciprocal;
+}
+
+bool icp_step_needs_events(const pclhip_icp* icp, int mode) {
+  if (icp->ctx->opt_step_events != 0 || icp->reciprocal || !icp->rejectors.empty()) return true;
+  if (icp->n == 0) return false;  // no search launch at all
+  return step_walks_served_groups(icp, mode) || lane_search_available(icp);
+}
+
+pclhip_status launch_step_start_stamp(pclhip_icp* icp) {
+  hipLaunchKernelGGL(icp_step_start_stamp_kernel, dim3(1), dim3(1), 0, icp->ctx->stream, icp->step_stamps);
+  PCLHIP_CHECK_HIP(icp->ctx, hipGetLastError());
+  return PCLHIP_OK;
+}
+
+// One iteration.  ICP_STEP_HOST: the host-driven form (T by value, the caller reads the record back).  The device-driven
+// forms: transform / restart / stop come from icp->ctl and the iteration is closed on the device (icp_solve_step), either
+// with ev[0..3] recorded before the search, after it, after the accumulation and after the solve (ICP_STEP_DEVICE_EVENTS),
+// or with nothing between the kernels (ICP_STEP_DEVICE_STAMPED: they stamp their own times into icp->step_stamps, and the
+// step record's sequence word tells the host that the step is done).
 pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d2, bool use_max, int mode,
-                                 hipEvent_t* ev) {
+                                 IcpStepKind kind, hipEvent_t* ev) {
   pclhip_ctx* ctx = icp->ctx;
   hipStream_t s = ctx->stream;
   const IndexView v = icp->target->view();
-  const bool device_loop = ev != nullptr;
+  const bool device_loop = kind != ICP_STEP_HOST;
+  const bool stamped = kind == ICP_STEP_DEVICE_STAMPED;
+  if (kind == ICP_STEP_DEVICE_EVENTS && ev == nullptr) return PCLHIP_ERR_INVALID;
+  if (stamped && (icp->step_stamps == nullptr || icp_step_needs_events(icp, mode))) return PCLHIP_ERR_INVALID;
+  unsigned long long* const stamps = stamped ? icp->step_stamps : nullptr;
+  // the marker between two launches of a step: an event of the step (event kind), the host-driven form's own, or nothing
+  const auto mark = [&](int k, hipEvent_t host_ev) {
+    if (stamped) return;
+    (void)hipEventRecord(device_loop ? ev[k] : host_ev, s);
+  };
   const IcpControl* ctl = device_loop ? icp->ctl : nullptr;
   Mat34 M;
   for (int i = 0; i < 12; ++i) M.m[i] = T ? T[i] : 0.0f;
@@ -2124,8 +2191,7 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
     const float so_from = icp->target->leaf_diag2;
     // target sharding in the device-driven loop: list the groups this rank serves in this launch, walk the list
     // (the reciprocal test searches the whole moved source: every group's working copy has to be current)
-    const bool owned = device_loop && icp->region.on != 0 && mode != PCLHIP_ICP_SYMMETRIC && ctx->opt_served_groups != 0 &&
-                       !icp->reciprocal;
+    const bool owned = device_loop && step_walks_served_groups(icp, mode);
     OwnedGroups og = {nullptr, nullptr, nullptr, nullptr};
     if (owned) {
       pclhip_status st = ensure_owned_groups(icp);
@@ -2149,7 +2215,7 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
       const uint32_t fill = search_fill_of(kflags);
       ngroups = (icp->n + fill - 1) / fill;
     }
-    (void)hipEventRecord(device_loop ? ev[0] : icp->ev0, s);
+    mark(0, icp->ev0);
     if (lane_now && !device_loop) {
       // nothing of this file
     } else if (owned) {
@@ -2186,7 +2252,7 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
       const pclhip_status lst = launch_lane_search(icp, M.m, ctl, order, bound, use_max);
       if (lst != PCLHIP_OK) return lst;
     }
-    (void)hipEventRecord(device_loop ? ev[1] : icp->ev_mid, s);
+    mark(1, icp->ev_mid);
     icp->mid_recorded = true;
     if (icp->search_only && !device_loop) {  // GeneralizedIterativeClosestPoint: its own passes follow (gicp.hpp)
       (void)hipEventRecord(icp->ev1, s);
@@ -2216,12 +2282,12 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
                          icp->n, icp->match_pos, icp->match_d2, keep, ctl, icp->enforce_same_direction_normals ? 1 : 0,
                          icp->partials, og);
     else if (mode == PCLHIP_ICP_POINT_TO_PLANE)
-      launch_accumulate<PCLHIP_ICP_POINT_TO_PLANE>(icp, v, ga, keep, M, ctl, s);
+      launch_accumulate<PCLHIP_ICP_POINT_TO_PLANE>(icp, v, ga, keep, M, ctl, stamps, s);
     else if (mode == PCLHIP_ICP_SYMMETRIC)
-      launch_accumulate<PCLHIP_ICP_SYMMETRIC>(icp, v, ga, keep, M, ctl, s);
+      launch_accumulate<PCLHIP_ICP_SYMMETRIC>(icp, v, ga, keep, M, ctl, stamps, s);
     else
-      launch_accumulate<PCLHIP_ICP_POINT_TO_POINT>(icp, v, ga, keep, M, ctl, s);
-    (void)hipEventRecord(device_loop ? ev[2] : icp->ev1, s);
+      launch_accumulate<PCLHIP_ICP_POINT_TO_POINT>(icp, v, ga, keep, M, ctl, stamps, s);
+    mark(2, icp->ev1);
     // (Folding this reduction into the accumulate kernel -- last block done -- was tried: the 2048 device-scope
     // atomics on one counter cost ~100 us across the 8 XCDs, five times this 20 us launch.)
     solved = device_loop && !icp_is_sharded(icp);  // no record to exchange: the reduction launch closes the iteration
@@ -2229,26 +2295,28 @@ pclhip_status launch_icp_iterate(pclhip_icp* icp, const float T[16], float max_d
     // search kernel ran (the served-group lists and the reciprocal search included; the per-lane kernels take no tickets).
     // Under sharding icp_solve_kernel follows, but nothing between the two is fed, so the re-arm stays here.
     PCLHIP_LAUNCH_REARM(ctx, icp_finalize_kernel, dim3(1), dim3(FINALIZE_THREADS), 0, s, icp->partials, ga, icp->sums_dev, ctl,
-                        solved ? icp->ctl : static_cast<IcpControl*>(nullptr), icp->steps, ctx->sched_ctr);
+                        solved ? icp->ctl : static_cast<IcpControl*>(nullptr), icp->steps, ctx->sched_ctr, stamps);
   } else {
     if (device_loop) {
-      (void)hipEventRecord(ev[0], s);
-      (void)hipEventRecord(ev[1], s);
+      mark(0, nullptr);
+      mark(1, nullptr);
     }
     if (filters) {  // an empty source share still takes part in the collectives of the chain's selection passes
       const pclhip_status es = apply_empty_shard_collectives(icp);
       if (es != PCLHIP_OK) return es;
     }
     PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(icp->sums_dev, 0, NS * sizeof(double), s));
-    if (device_loop) (void)hipEventRecord(ev[2], s);
+    if (device_loop) mark(2, nullptr);
   }
   PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   // multi-GPU: the record is summed over the ranks on this stream, between the reduction and the solve
   pclhip_status st = allreduce_record(icp);
   if (st != PCLHIP_OK) return st;
   if (device_loop) {
-    if (!solved) hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(64), 0, s, icp->ctl, icp->sums_dev, icp->steps);
-    (void)hipEventRecord(ev[3], s);
+    if (!solved)
+      hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(64), 0, s, icp->ctl, icp->sums_dev, icp->steps, stamps,
+                         icp->n == 0 ? 1 : 0);
+    mark(3, nullptr);
     PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   }
   return PCLHIP_OK;
