@@ -298,6 +298,37 @@ PCLHIP_API pclhip_status pclhip_fpfh(pclhip_index* index, const int32_t* indices
                                      void* out, size_t out_stride_bytes, float* out_spfh, uint64_t* out_nan_count);
 /* GPU time (ms) of the SPFH kernel and of the weighting kernel of the last pclhip_fpfh on this index. */
 PCLHIP_API void pclhip_index_last_fpfh_ms(const pclhip_index* index, double* spfh_ms, double* weight_ms);
+/* pcl::ISSKeypoint3D<PointInT, PointOutT>::detectKeypoints without boundary estimation (keypoints/include/pcl/keypoints/
+ * impl/iss_3d.hpp:164-208, 302-473; border_radius == 0): search surface == input.  A neighbourhood is every indexed point
+ * with float d2 < float(r * r), the point itself included (as pclhip_radius_search).
+ *   1. Per finite point i with m >= min_neighbors points within salient_radius: C = sum (p_j - p_i)(p_j - p_i)^T with the
+ *      coordinates widened to double before the subtraction and all sums in double; eigenvalues e1 >= e2 >= e3 in double;
+ *      the saliency is s_i = e3 iff e2 / e1 < gamma_21 && e3 / e2 < gamma_32 (both in double, a NaN ratio fails), else 0.
+ *   2. A point with s_i > 0 is a keypoint iff its non_max_radius neighbourhood holds >= min_neighbors points and no
+ *      neighbour j has s_i < s_j (strict: equal saliencies all win).
+ *   3. out_indices receives the keypoints' original indices, ascending (the reference's order with one thread).
+ *   out_indices      (host or device) room for `capacity` ids; *n_keypoints is always written, a capacity that is too
+ *                    small gives PCLHIP_ERR_OVERFLOW after it is (n_orig always suffices)
+ *   out_saliency     (host or device, optional) n_orig doubles: s_i, 0 for a record that is not salient (a non-finite one
+ *                    included)
+ *   out_eigenvalues  (host or device, optional) 3 * n_orig doubles, descending: 0, 0, 0 below min_neighbors, NaN for a
+ *                    non-finite record
+ * A radius, gamma or min_neighbors that is <= 0 or not finite is PCLHIP_ERR_INVALID (ISSKeypoint3D::initCompute refuses
+ * them).  A positive radius whose float square is 0 is a valid call in which no point has a neighbour, not even itself:
+ * m = 0 < min_neighbors, no keypoints.  The index must cover the whole unscaled cloud: one built with `indices` or with
+ * rescale values is PCLHIP_ERR_STATE.
+ * Deviations: a point with e3 < 0 or a non-finite eigenvalue is not salient (the reference skips the store and later reads
+ * uninitialised memory for it); boundary estimation (border_radius > 0, normal_radius) is not built; non-finite records
+ * are never keypoints and never neighbours; the eigenvalues come from a cyclic Jacobi iteration in double and the sums run
+ * in traversal order (the reference: Eigen's QR iteration, ascending distance) -- each eigenvalue lies within
+ * (m + 32) * 2^-53 * trace(C) of the exact one.  Two calls give the same bytes.
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_iss_ms that of its two passes. */
+PCLHIP_API pclhip_status pclhip_iss_keypoints(pclhip_index* index, double salient_radius, double non_max_radius,
+                                              double gamma_21, double gamma_32, int min_neighbors, int32_t* out_indices,
+                                              uint64_t capacity, uint64_t* n_keypoints, double* out_saliency,
+                                              double* out_eigenvalues);
+/* GPU time (ms) of the scatter kernel and of the non-maximum kernel of the last pclhip_iss_keypoints on this index. */
+PCLHIP_API void pclhip_index_last_iss_ms(const pclhip_index* index, double* scatter_ms, double* nms_ms);
 /* pcl::EuclideanClusterExtraction<PointT>::extract (segmentation/.../impl/extract_clusters.hpp:124-253): the clusters are
  * the connected components of the graph over the index's points with an edge wherever float d2 < float(r * r),
  * r = double(float(tolerance)) -- the relation of pclhip_radius_search.  The index defines the set of points: built with

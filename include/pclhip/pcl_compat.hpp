@@ -1966,6 +1966,129 @@ class EuclideanClusterExtraction : public PCLBase<PointT> {
   std::string error_;
 };
 
+// pcl::Keypoint<PointInT, PointOutT> (keypoints/include/pcl/keypoints/keypoint.h:52-209): compute() checks the input, calls
+// the detector's detectKeypoints() and leaves the keypoints' indices behind for getKeypointsIndices().
+template <typename PointInT, typename PointOutT>
+class Keypoint : public PCLBase<PointInT> {
+ public:
+  using KdTree = search::Search<PointInT>;
+  using KdTreePtr = typename KdTree::Ptr;
+  using PointCloudOut = PointCloud<PointOutT>;
+  void setSearchMethod(const KdTreePtr& tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setSearchSurface(const typename PointCloud<PointInT>::ConstPtr& cloud) { surface_ = cloud; }
+  typename PointCloud<PointInT>::ConstPtr getSearchSurface() const { return surface_; }
+  PointIndices::ConstPtr getKeypointsIndices() const { return keypoints_indices_; }
+  const std::string& getLastError() const { return error_; }
+  void compute(PointCloudOut& output) {  // impl/keypoint.hpp:123-147
+    output.points.clear();
+    output.width = 0;
+    output.height = 1;
+    output.is_dense = true;
+    keypoints_indices_ = std::make_shared<PointIndices>();
+    error_.clear();
+    if (!initCompute()) return;
+    detectKeypoints(output);
+  }
+ protected:
+  virtual bool initCompute() { return bool(this->input_); }
+  virtual void detectKeypoints(PointCloudOut& output) = 0;
+  KdTreePtr tree_;
+  typename PointCloud<PointInT>::ConstPtr surface_;
+  std::shared_ptr<PointIndices> keypoints_indices_ = std::make_shared<PointIndices>();
+  std::string error_;
+};
+
+// pcl::ISSKeypoint3D<PointInT, PointOutT> (keypoints/include/pcl/keypoints/iss_3d.h, impl/iss_3d.hpp:164-253, 302-473)
+// without boundary estimation, over pclhip_iss_keypoints: the keypoints in ascending index order (the reference's with one
+// thread).  compute() leaves the output empty and says why in getLastError() for what this path does not build: a positive
+// border radius (BoundaryEstimation and the normals behind it), setIndices, another search surface, a foreign Search.
+template <typename PointInT, typename PointOutT = PointInT>
+class ISSKeypoint3D : public Keypoint<PointInT, PointOutT> {
+ public:
+  using PointCloudOut = typename Keypoint<PointInT, PointOutT>::PointCloudOut;
+  ISSKeypoint3D(double salient_radius = 0.0001) : ISSKeypoint3D(Context::defaultContext(), salient_radius) {}
+  explicit ISSKeypoint3D(Context::Ptr ctx, double salient_radius = 0.0001) : ctx_(std::move(ctx)), salient_radius_(salient_radius) {}
+  void setSalientRadius(double r) { salient_radius_ = r; }
+  void setNonMaxRadius(double r) { non_max_radius_ = r; }
+  void setNormalRadius(double r) { normal_radius_ = r; }
+  void setBorderRadius(double r) { border_radius_ = r; }
+  void setThreshold21(double gamma_21) { gamma_21_ = gamma_21; }
+  void setThreshold32(double gamma_32) { gamma_32_ = gamma_32; }
+  void setMinNeighbors(int min_neighbors) { min_neighbors_ = min_neighbors; }
+  void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }  // only stored
+  unsigned int getNumberOfThreads() const { return threads_; }
+  // per record of the input, after compute(): the saliency (0: not salient) and the eigenvalues of its scatter matrix
+  const std::vector<double>& getSaliency() const { return saliency_; }
+  const std::vector<double>& getEigenvalues() const { return eigenvalues_; }
+
+ protected:
+  bool initCompute() override {  // impl/iss_3d.hpp:213-253
+    if (!Keypoint<PointInT, PointOutT>::initCompute()) return false;
+    const char* why = nullptr;
+    if (!(salient_radius_ > 0.0)) why = "the salient radius must be > 0";
+    else if (!(non_max_radius_ > 0.0)) why = "the non maxima radius must be > 0";
+    else if (!(gamma_21_ > 0.0) || !(gamma_32_ > 0.0)) why = "the thresholds must be > 0";
+    else if (min_neighbors_ <= 0) why = "the minimum number of neighbors must be > 0";
+    else if (border_radius_ > 0.0 || normal_radius_ > 0.0) why = "boundary estimation (border_radius, normal_radius > 0) is not built";
+    else if (this->indices_ && !this->fake_indices_) why = "setIndices is not built";
+    else if (this->surface_ && this->surface_ != this->input_) why = "a search surface other than the input is not built";
+    else if (!ctx_ || !ctx_->ok()) why = "no device";
+    if (why != nullptr) this->error_ = why;
+    return why == nullptr;
+  }
+  void detectKeypoints(PointCloudOut& output) override {
+    const auto& input = this->input_;
+    if (!this->tree_) this->tree_ = std::make_shared<search::KdTree<PointInT>>(ctx_);
+    auto* dev = dynamic_cast<search::KdTree<PointInT>*>(this->tree_.get());
+    if (dev == nullptr) {
+      this->error_ = "the search method is not a pclhip::search::KdTree";
+      return;
+    }
+    if (dev->getInputCloud() != input || dev->handle() == nullptr) {
+      if (!dev->setInputCloud(input)) {
+        this->error_ = pclhip_last_error(ctx_->get());
+        return;
+      }
+    }
+    const std::size_t n = input->size();
+    Indices& idx = this->keypoints_indices_->indices;
+    idx.resize(n);
+    saliency_.assign(n, 0.0);
+    eigenvalues_.assign(3 * n, 0.0);
+    std::uint64_t k = 0;
+    if (pclhip_iss_keypoints(dev->handle(), salient_radius_, non_max_radius_, gamma_21_, gamma_32_, min_neighbors_, idx.data(),
+                             n, &k, saliency_.data(), eigenvalues_.data()) != PCLHIP_OK) {
+      this->error_ = pclhip_last_error(dev->context()->get());
+      idx.clear();
+      return;
+    }
+    idx.resize(std::size_t(k));
+    output.points.reserve(idx.size());
+    for (const index_t i : idx) {  // impl/iss_3d.hpp:461-466
+      PointOutT p{};
+      p.x = (*input)[std::size_t(i)].x;
+      p.y = (*input)[std::size_t(i)].y;
+      p.z = (*input)[std::size_t(i)].z;
+      output.push_back(p);
+    }
+    output.height = 1;
+    output.is_dense = true;
+  }
+
+ private:
+  Context::Ptr ctx_;
+  double salient_radius_;
+  double non_max_radius_ = 0.0;  // iss_3d.h:117-131: the reference's defaults
+  double normal_radius_ = 0.0;
+  double border_radius_ = 0.0;
+  double gamma_21_ = 0.975;
+  double gamma_32_ = 0.975;
+  int min_neighbors_ = 5;
+  unsigned int threads_ = 0;
+  std::vector<double> saliency_, eigenvalues_;
+};
+
 // ---- pcl::ModelCoefficients (common/include/pcl/ModelCoefficients.h; `values` only), the model and method constants
 // (sample_consensus/model_types.h:45-47, method_types.h:45) and pcl::SACSegmentation<PointT> (segmentation/include/pcl/
 // segmentation/sac_segmentation.h:77-330, impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC over

@@ -8,7 +8,7 @@ from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_PLANE, S
 from .api import (Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
-                  IterativeClosestPoint,
+                  ISSKeypoint3D, IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
                   RadiusOutlierRemoval, SACSegmentation, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,

@@ -6,6 +6,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::IterativeClosestPoint / ...WithNormals          registration/include/pcl/registration/icp.h:98-347,360-440
   pcl::NormalEstimation                                features/include/pcl/features/normal_3d.h:243-420
   pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
+  pcl::ISSKeypoint3D                                   keypoints/include/pcl/keypoints/iss_3d.h
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
   pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
   pcl::SACSegmentation (planes, RANSAC)                segmentation/include/pcl/segmentation/sac_segmentation.h:77-330
@@ -2061,6 +2062,123 @@ class FPFHEstimation:
     def computeBoth(self):
         """-> ((m, 33) FPFH, (n, 33) SPFH) of one call."""
         return self._run(True, True)
+
+
+class ISSKeypoint3D:
+    """pcl::ISSKeypoint3D<PointInT, PointOutT> without boundary estimation (keypoints/include/pcl/keypoints/iss_3d.h,
+    impl/iss_3d.hpp:164-208, 302-473) over pclhip_iss_keypoints.  The input is an (n, c >= 3) float32 cloud, numpy or a
+    torch CUDA tensor; the keypoint indices come back ascending, in the same kind of array."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.tree = None
+        self.cloud = None
+        self.salient_radius = 0.0      # iss_3d.h:117-131: the reference's defaults
+        self.non_max_radius = 0.0
+        self.gamma_21 = 0.975
+        self.gamma_32 = 0.975
+        self.min_neighbors = 5
+        self._indices = None
+        self._saliency = None
+        self._eigenvalues = None
+
+    def getClassName(self):
+        return "ISSKeypoint3D"
+
+    def setInputCloud(self, cloud):
+        self.cloud = cloud
+
+    def getInputCloud(self):
+        return self.cloud
+
+    def setSearchMethod(self, tree):
+        """An index over the same whole, unscaled cloud (a KdTree another stage built) is reused as it is."""
+        self.tree = tree
+
+    def getSearchMethod(self):
+        return self.tree
+
+    def setSalientRadius(self, r):
+        self.salient_radius = float(r)
+
+    def setNonMaxRadius(self, r):
+        self.non_max_radius = float(r)
+
+    def setThreshold21(self, gamma_21):
+        self.gamma_21 = float(gamma_21)
+
+    def setThreshold32(self, gamma_32):
+        self.gamma_32 = float(gamma_32)
+
+    def setMinNeighbors(self, n):
+        self.min_neighbors = int(n)
+
+    def setBorderRadius(self, r):
+        if float(r) > 0.0:
+            raise NotImplementedError("ISSKeypoint3D: boundary estimation (border_radius > 0) is not built")
+
+    def setNormalRadius(self, r):
+        if float(r) > 0.0:
+            raise NotImplementedError("ISSKeypoint3D: boundary estimation (normal_radius > 0) is not built")
+
+    def setNumberOfThreads(self, n=0):
+        pass
+
+    def lastPassMs(self):
+        """GPU time (ms) of the scatter kernel and of the non-maximum kernel of the last compute()."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self.lib.pclhip_index_last_iss_ms(self.tree.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def lastKernelMs(self):
+        return float(self.lib.pclhip_index_last_kernel_ms(self.tree.h))
+
+    def _run(self, want_saliency, want_eigenvalues):
+        assert self.cloud is not None, "setInputCloud first"
+        if self.tree is None:
+            self.tree = KdTree(self.ctx)
+        if self.tree.h is None or self.tree._cloud_id != (id(self.cloud), None):
+            self.tree.setInputCloud(self.cloud)
+        n = self.tree.n_cloud
+        if _is_torch(self.cloud):
+            import torch
+
+            def make(shape, dtype):
+                t = torch.empty(shape, dtype={np.int32: torch.int32, np.float64: torch.float64}[dtype],
+                                device=self.cloud.device)
+                return t, C.c_void_p(t.data_ptr())
+        else:
+            def make(shape, dtype):
+                a = np.empty(shape, dtype)
+                return a, C.c_void_p(a.ctypes.data)
+        idx, ip = make(max(n, 1), np.int32)
+        sal, sp = make(n, np.float64) if want_saliency else (None, None)
+        eig, ep = make((n, 3), np.float64) if want_eigenvalues else (None, None)
+        k = C.c_uint64(0)
+        check(self.lib.pclhip_iss_keypoints(self.tree.h, self.salient_radius, self.non_max_radius, self.gamma_21,
+                                            self.gamma_32, self.min_neighbors, ip, n, C.byref(k), sp, ep), self.ctx.h)
+        self._indices = idx[:k.value]
+        self._saliency, self._eigenvalues = sal, eig
+        return self._indices
+
+    def compute(self):
+        """-> int32 [k]: the keypoints' indices into the input cloud, ascending."""
+        return self._run(False, False)
+
+    def computeAll(self):
+        """-> (indices int32 [k], saliency float64 [n], eigenvalues float64 [n, 3] descending) of one call."""
+        idx = self._run(True, True)
+        return idx, self._saliency, self._eigenvalues
+
+    def getKeypointsIndices(self):
+        return self._indices
+
+    def getKeypoints(self):
+        """The records of the input cloud at the keypoints of the last compute()."""
+        if _is_torch(self.cloud):
+            return self.cloud[self._indices.long()]
+        return np.asarray(self.cloud)[self._indices]
 
 
 class EuclideanClusterExtraction:

@@ -684,6 +684,7 @@ pclhip_status pclhip_index_build_ex(pclhip_ctx* ctx, const void* points, size_t 
   pclhip_index* ix = new pclhip_index();
   ix->ctx = ctx;
   ix->n_orig = n;
+  ix->subset = indices != nullptr;
   if (scale) {
     ix->scaled = true;
     for (int d = 0; d < 3; ++d) ix->scale[d] = scale[d];
@@ -1391,6 +1392,35 @@ pclhip_status pclhip_fpfh(pclhip_index* ix, const int32_t* indices, uint64_t n_i
 void pclhip_index_last_fpfh_ms(const pclhip_index* ix, double* spfh_ms, double* weight_ms) {
   if (spfh_ms) *spfh_ms = ix ? ix->fpfh_pass_ms[0] : 0.0;
   if (weight_ms) *weight_ms = ix ? ix->fpfh_pass_ms[1] : 0.0;
+}
+
+// ---- ISSKeypoint3D (iss.hpp) -----------------------------------------------------------------------
+pclhip_status pclhip_iss_keypoints(pclhip_index* ix, double salient_radius, double non_max_radius, double gamma_21,
+                                   double gamma_32, int min_neighbors, int32_t* out_indices, uint64_t capacity,
+                                   uint64_t* n_keypoints, double* out_saliency, double* out_eigenvalues) {
+  if (!ix || !n_keypoints) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_keypoints = 0;
+  // ISSKeypoint3D::initCompute (iss_3d.hpp:213-253) refuses each of these
+  PCLHIP_REQUIRE(ctx, std::isfinite(salient_radius) && salient_radius > 0.0, "the salient radius must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, std::isfinite(non_max_radius) && non_max_radius > 0.0, "the non maxima radius must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, std::isfinite(gamma_21) && gamma_21 > 0.0, "gamma_21 must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, std::isfinite(gamma_32) && gamma_32 > 0.0, "gamma_32 must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, min_neighbors > 0, "min_neighbors must be > 0");
+  PCLHIP_REQUIRE(ctx, out_indices != nullptr || capacity == 0, "null buffer");
+  if (ix->scaled || ix->subset) {
+    set_error(ctx, "ISS keypoints need an index built over the whole cloud in its own coordinates (no indices, no rescaling)");
+    return PCLHIP_ERR_STATE;
+  }
+  // radiusSearch keeps d2 < float(r * r) (kdtree_flann.hpp:398)
+  return iss_keypoints(ix, float(salient_radius * salient_radius), float(non_max_radius * non_max_radius), gamma_21, gamma_32,
+                       uint32_t(min_neighbors), out_indices, capacity, n_keypoints, out_saliency, out_eigenvalues);
+}
+
+void pclhip_index_last_iss_ms(const pclhip_index* ix, double* scatter_ms, double* nms_ms) {
+  if (scatter_ms) *scatter_ms = ix ? ix->iss_pass_ms[0] : 0.0;
+  if (nms_ms) *nms_ms = ix ? ix->iss_pass_ms[1] : 0.0;
 }
 
 // ---- EuclideanClusterExtraction (cluster.hpp) ------------------------------------------------------

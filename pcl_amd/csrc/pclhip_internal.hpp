@@ -299,10 +299,12 @@ struct pclhip_index {
   double build_ms = 0;
   double last_kernel_ms = 0;
   double fpfh_pass_ms[2] = {0, 0};  // the SPFH and the weighting kernel of the last pclhip_fpfh
+  double iss_pass_ms[2] = {0, 0};   // the scatter and the non-max kernel of the last pclhip_iss_keypoints
   double cluster_ms[2] = {0, 0};    // the hook and the flatten kernel of the last pclhip_euclidean_clusters
   uint64_t cluster_unions = 0;      // ... and the unions its hook kernel attempted
   bool has_normals = false;
   bool scaled = false;              // built through a rescaling point representation: coordinates * scale
+  bool subset = false;              // built with `indices`: it holds a selection of the cloud's records
   float scale[3] = {1, 1, 1};
   pclhip::IndexView view() const;
 };
@@ -587,6 +589,10 @@ pclhip_status outlier_filter(pclhip_index* ix, const int32_t* indices, uint64_t 
 // rows per original record to out_spfh (optional)
 pclhip_status fpfh_compute(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius, void* out,
                            size_t out_stride, float* out_spfh, uint64_t* out_nan_count);
+// ISSKeypoint3D over the index (iss.hpp, compiled into radius.hip): t_sal and t_nms are the float squares of the radii
+pclhip_status iss_keypoints(pclhip_index* ix, float t_sal, float t_nms, double g21, double g32, uint32_t min_nb,
+                            int32_t* out_indices, uint64_t capacity, uint64_t* n_keypoints, double* out_saliency,
+                            double* out_eigenvalues);
 // EuclideanClusterExtraction over the index (cluster.hpp, compiled into radius.hip): the components of d2 < t
 pclhip_status euclidean_clusters(pclhip_index* ix, float t, uint32_t min_size, uint32_t max_size, int32_t* out_labels,
                                  uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices,

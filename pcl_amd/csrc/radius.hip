@@ -434,6 +434,9 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // FPFHEstimation: two radius traversals of the index with per-point histograms
 #include "fpfh.hpp"
 
+// ISSKeypoint3D: two radius traversals of the index, scatter eigenvalues and non-maximum suppression
+#include "iss.hpp"
+
 // EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
 #include "cluster.hpp"
 
