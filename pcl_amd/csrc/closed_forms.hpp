@@ -5,7 +5,7 @@
 //     (registration/include/pcl/registration/impl/transformation_estimation_point_to_plane_lls.hpp:132-163,247-268)
 //   * the symmetric objective's solve
 //     (impl/transformation_estimation_symmetric_point_to_plane_lls.hpp:128-147,192-196)
-//   * umeyama from raw sums (common/include/pcl/common/impl/eigen.hpp:675-738)
+//   * umeyama from raw sums (common/include/pcl/common/impl/eigen.hpp:675-738), its SVD a one-sided Jacobi
 //   * float 4x4 product for final_transformation_ (registration/include/pcl/registration/impl/icp.hpp:223)
 //   * DefaultConvergenceCriteria::hasConverged (impl/default_convergence_criteria.hpp:49-140)
 // Everything is plain IEEE double arithmetic in a fixed order (-ffp-contract=off on both sides); the only
@@ -123,92 +123,116 @@ PCLHIP_HD void jacobi_eig3(double A[3][3], double V[3][3], double w[3]) {
   for (int i = 0; i < 3; ++i) w[i] = A[i][i];
 }
 
-PCLHIP_HD double det3(const double M[3][3]) {
-  return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-         M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-}
-
 PCLHIP_HD void cross3(const double a[3], const double b[3], double c[3]) {
   c[0] = a[1] * b[2] - a[2] * b[1];
   c[1] = a[2] * b[0] - a[0] * b[2];
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// R = U S V^T of sigma via the eigen-decomposition of sigma^T sigma (V, singular values) and
-// U = sigma V / s, with the umeyama reflection fix on the smallest singular direction.
+// R = U S V^T of umeyama (eigen.hpp:700-724), S = diag(1, 1, det(U) det(V)), as
+//   R = u0 v0^T + u1 v1^T + (u0 x u1)(v0 x v1)^T,
+// which is U S V^T for every rank of sigma and either sign of the two determinants: the third pair never enters, so
+// a sigma of rank two (a wall, a floor) or one (a pole) gives a proper rotation like any other.
+// The SVD is a one-sided Jacobi on sigma ITSELF (Hestenes: plane rotations from the right until the columns are
+// orthogonal; the columns are then u_c * sv_c and the product of the rotations is V), NOT the eigen-decomposition of
+// sigma^T sigma: that squares the condition number, the square root of an eigenvalue that is rounding noise is 1e-8 of
+// sv0, and a column of U normalised from it is the direction of the noise, not orthogonal to the others (a planar
+// cloud then gives max|R^T R - I| of 0.9; tests/test_solver_regimes.py).  On sigma a small column keeps the relative
+// accuracy of sigma's own entries (a rod of relative thickness 1e-5 has sv1 = 1e-10 sv0 and needs it: an arbitrary turn
+// about its axis costs 1e-5 of residual), and a column that IS noise is still orthogonal to the others when the
+// rotations end, so it completes a rotation as well as any other unit vector would.
+// Where sigma has rank one the rotation about the line is free: the one returned takes V's second column, as the
+// rotations left it, to the normalised second column of sigma V if that is not zero (rounding noise, in general), else
+// to u0 x e for the axis e in which u0 is smallest.  sigma == 0 gives the identity.
+// Every index below is a compile-time constant after unrolling (see lu_solve6).
 PCLHIP_HD void rotation_from_sigma(const double sigma[3][3], double R[3][3]) {
-  double AtA[3][3];
+  double B[3][3], V[3][3];
+#pragma unroll
   for (int i = 0; i < 3; ++i)
+#pragma unroll
     for (int j = 0; j < 3; ++j) {
-      double s = 0;
-      for (int k = 0; k < 3; ++k) s += sigma[k][i] * sigma[k][j];
-      AtA[i][j] = s;
+      B[i][j] = sigma[i][j];
+      V[i][j] = (i == j) ? 1.0 : 0.0;
     }
-  double V[3][3], w[3];
-  jacobi_eig3(AtA, V, w);
-  // descending eigenvalues: selection by exchanges of whole (value, vector) pairs -- constant indices only
+  // A pair of columns is left alone once its cosine is below 2^-53; the convergence is quadratic (4-6 sweeps)
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = p + 1; q < 3; ++q) {
+        const double alpha = B[0][p] * B[0][p] + B[1][p] * B[1][p] + B[2][p] * B[2][p];
+        const double beta = B[0][q] * B[0][q] + B[1][q] * B[1][q] + B[2][q] * B[2][q];
+        const double gamma = B[0][p] * B[0][q] + B[1][p] * B[1][q] + B[2][p] * B[2][q];
+        if (!(fabs(gamma) > 0x1p-53 * (sqrt(alpha) * sqrt(beta)))) continue;
+        rotated = true;
+        const double zeta = (beta - alpha) / (2.0 * gamma);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double bp = B[k][p], bq = B[k][q], vp = V[k][p], vq = V[k][q];
+          B[k][p] = c * bp - s * bq;
+          B[k][q] = s * bp + c * bq;
+          V[k][p] = c * vp - s * vq;
+          V[k][q] = s * vp + c * vq;
+        }
+      }
+    if (!rotated) break;
+  }
+  double n[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) n[c] = sqrt(B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c]);
+  // descending singular values: exchanges of whole (norm, column of B, column of V) triples -- constant indices only
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = i + 1; j < 3; ++j) {
-      const bool sw = w[j] > w[i];
-      const double wi = w[i], wj = w[j];
-      w[i] = sw ? wj : wi;
-      w[j] = sw ? wi : wj;
+      const bool sw = n[j] > n[i];
+      const double ni = n[i], nj = n[j];
+      n[i] = sw ? nj : ni;
+      n[j] = sw ? ni : nj;
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const double vi = V[r][i], vj = V[r][j];
+        const double bi = B[r][i], bj = B[r][j], vi = V[r][i], vj = V[r][j];
+        B[r][i] = sw ? bj : bi;
+        B[r][j] = sw ? bi : bj;
         V[r][i] = sw ? vj : vi;
         V[r][j] = sw ? vi : vj;
       }
     }
-  double Vs[3][3], sv[3];
+  if (!(n[0] > 0)) {  // sigma == 0 (coincident points, one pair), or not finite
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    sv[c] = sqrt(w[c] > 0 ? w[c] : 0.0);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) Vs[r][c] = V[r][c];
-  }
-  if (det3(Vs) < 0)  // keep V a proper rotation; the sign moves into U, U S V^T is unchanged
-    for (int r = 0; r < 3; ++r) Vs[r][2] = -Vs[r][2];
-  double U[3][3];
-  const double tol = 1e-13 * (sv[0] > 0 ? sv[0] : 1.0);
-  for (int c = 0; c < 3; ++c) {
-    double u[3];
-    for (int r = 0; r < 3; ++r) u[r] = sigma[r][0] * Vs[0][c] + sigma[r][1] * Vs[1][c] + sigma[r][2] * Vs[2][c];
-    const double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    for (int r = 0; r < 3; ++r) U[r][c] = (sv[c] > tol && n > 0) ? u[r] / n : 0.0;
-  }
-  // complete rank-deficient cases with cross products (right-handed completion)
-  if (!(sv[0] > tol)) {
     for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) U[i][j] = (i == j) ? 1.0 : 0.0;
-  } else {
-    double u0[3] = {U[0][0], U[1][0], U[2][0]}, u1[3], u2[3];
-    if (!(sv[1] > tol)) {
-      int mi = 0;
-      double least = fabs(u0[0]);
 #pragma unroll
-      for (int d = 1; d < 3; ++d)
-        if (fabs(u0[d]) < least) {
-          least = fabs(u0[d]);
-          mi = d;
-        }
-      const double e[3] = {mi == 0 ? 1.0 : 0.0, mi == 1 ? 1.0 : 0.0, mi == 2 ? 1.0 : 0.0};
-      cross3(u0, e, u1);
-      const double n = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-      for (int d = 0; d < 3; ++d) U[d][1] = u1[d] / n;
-    }
-    for (int d = 0; d < 3; ++d) u1[d] = U[d][1];
-    if (!(sv[2] > tol)) {
-      cross3(u0, u1, u2);
-      for (int d = 0; d < 3; ++d) U[d][2] = u2[d];
-    }
+      for (int j = 0; j < 3; ++j) R[i][j] = (i == j) ? 1.0 : 0.0;
+    return;
   }
-  // eigen.hpp:716-724: S = diag(1,1,-1) if det(U) det(V) < 0
-  const double sgn = (det3(U) * det3(Vs) < 0) ? -1.0 : 1.0;
+  const double v0[3] = {V[0][0], V[1][0], V[2][0]}, v1[3] = {V[0][1], V[1][1], V[2][1]};
+  const double u0[3] = {B[0][0] / n[0], B[1][0] / n[0], B[2][0] / n[0]};
+  double u1[3], u2[3], v2[3];
+  // No product of the inputs is as small as 1e-100 of the largest unless it underflowed or is an exact zero; a column
+  // above that is orthogonal to u0 to 2^-53 already, the Gram-Schmidt step takes off what the rotations after its last
+  // one put back.
+  if (n[1] > 1e-100 * n[0]) {
+    const double d = (B[0][1] * u0[0] + B[1][1] * u0[1] + B[2][1] * u0[2]) / n[1];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) u1[r] = B[r][1] / n[1] - d * u0[r];
+  } else {
+    const double a0 = fabs(u0[0]), a1 = fabs(u0[1]), a2 = fabs(u0[2]);
+    const bool m0 = a0 <= a1 && a0 <= a2, m1 = !m0 && a1 <= a2;
+    const double e[3] = {m0 ? 1.0 : 0.0, m1 ? 1.0 : 0.0, (m0 || m1) ? 0.0 : 1.0};
+    cross3(u0, e, u1);
+  }
+  const double l1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) u1[r] /= l1;
+  cross3(u0, u1, u2);
+  cross3(v0, v1, v2);
+#pragma unroll
   for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * Vs[j][0] + U[i][1] * Vs[j][1] + sgn * U[i][2] * Vs[j][2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[i][j] = u0[i] * v0[j] + u1[i] * v1[j] + u2[i] * v2[j];
 }
 
 PCLHIP_HD void load_normal_system(const double* s, double A[6][6], double b[6]) {
