@@ -329,6 +329,45 @@ PCLHIP_API pclhip_status pclhip_iss_keypoints(pclhip_index* index, double salien
                                               double* out_eigenvalues);
 /* GPU time (ms) of the scatter kernel and of the non-maximum kernel of the last pclhip_iss_keypoints on this index. */
 PCLHIP_API void pclhip_index_last_iss_ms(const pclhip_index* index, double* scatter_ms, double* nms_ms);
+/* pcl::MovingLeastSquares<PointInT, PointOutT>::process (surface/include/pcl/surface/mls.h, impl/mls.hpp: process,
+ * performProcessing, computeMLSPointNormal, MLSResult::computeMLSSurface and ::projectQueryPoint) with
+ * setUpsamplingMethod(NONE), polynomial_order 0, 1 or 2 and projection_method NONE or SIMPLE: search surface == input.  A
+ * neighbourhood is every indexed point with float d2 < float(r * r), the point itself included (as pclhip_radius_search).
+ * Per indexed point q with m neighbours, in ascending original index:
+ *   1. m < 3: no output record.
+ *   2. Plane: the centroid c and C = sum (p_j - c)(p_j - c)^T in double; the smallest eigenvalue l0 of C and its unit
+ *      eigenvector n; mean = q - ((q - c) . n) n; curvature = |l0 / trace(C)| (0 when the trace is 0);
+ *      v = unitOrthogonal(n) by Eigen's rule for 3-vectors, u = n x v.
+ *   3. Fit, only with polynomial_order == 2 and m >= 6: d = p_j - mean, w = exp(-d.d / sqr_gauss_param),
+ *      (u_j, v_j, f_j) = (d.u, d.v, d.n), P_j = (1, v, v^2, u, uv, u^2); (sum w P P^T) coeff = sum w P f by Cholesky in
+ *      double.  A pivot that is not positive or a coeff[0] that is not finite leaves the point with its plane.
+ *   4. With a fit and PCLHIP_MLS_SIMPLE: point = mean + coeff[0] n, normal = normalize(n - coeff[3] u - coeff[1] v);
+ *      otherwise point = mean, normal = n.
+ *   out_points   (host or device, optional) 3 floats per output record
+ *   out_normals  (host or device, optional: setComputeNormals) 4 floats per output record: nx ny nz curvature
+ *   out_indices  (host or device, optional) corresponding_input_indices: the record's original index, ascending
+ *   out_double   (host or device, optional) 8 doubles per output record, unrounded: point (3), normal (3), curvature, m
+ * Each has room for `capacity` records; *n_out is always written, a capacity that is too small gives
+ * PCLHIP_ERR_OVERFLOW after it is (n_orig always suffices).
+ * search_radius or sqr_gauss_param <= 0 or not finite, an order outside 0 .. 2 and the ORTHOGONAL projection are
+ * PCLHIP_ERR_INVALID with an empty output.  A positive radius whose float square is 0 is a valid call in which no point
+ * has a neighbour: no output.  The index must cover the whole unscaled cloud: one built with `indices` or with rescale
+ * values is PCLHIP_ERR_STATE.
+ * Deviations: the sign of n is a function of C alone -- its component of largest magnitude is positive, ties go to the
+ * lowest axis (the reference's eigen33 leaves the sign to its cross products; points and curvature do not depend on it);
+ * the sums run in traversal order, one-pass and shifted by the query, the 6 x 6 matrix is assembled from 15 moments (the
+ * reference: ascending distance, two-pass, P diag(w) P^T); the eigenvector comes from a cyclic Jacobi iteration (the
+ * reference: the closed-form eigen33); non-finite records are neither queries nor neighbours and produce no output.  Not
+ * built: the ORTHOGONAL projection (the reference's Newton loop, impl/mls.hpp:551-579, has no iteration cap), order > 2,
+ * upsampling, setIndices, another search surface, cached MLS results.  Two calls give the same bytes.
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_mls_ms that of its two passes. */
+enum { PCLHIP_MLS_NONE = 0, PCLHIP_MLS_SIMPLE = 1, PCLHIP_MLS_ORTHOGONAL = 2 }; /* MLSResult::ProjectionMethod */
+PCLHIP_API pclhip_status pclhip_mls_process(pclhip_index* index, double search_radius, double sqr_gauss_param,
+                                            int polynomial_order, int projection_method, float* out_points,
+                                            float* out_normals, int32_t* out_indices, uint64_t capacity, uint64_t* n_out,
+                                            double* out_double);
+/* GPU time (ms) of the plane kernel and of the fit kernel (0 when it did not run) of the last pclhip_mls_process. */
+PCLHIP_API void pclhip_index_last_mls_ms(const pclhip_index* index, double* plane_ms, double* fit_ms);
 /* pcl::EuclideanClusterExtraction<PointT>::extract (segmentation/.../impl/extract_clusters.hpp:124-253): the clusters are
  * the connected components of the graph over the index's points with an edge wherever float d2 < float(r * r),
  * r = double(float(tolerance)) -- the relation of pclhip_radius_search.  The index defines the set of points: built with

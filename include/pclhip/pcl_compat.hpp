@@ -2089,6 +2089,134 @@ class ISSKeypoint3D : public Keypoint<PointInT, PointOutT> {
   std::vector<double> saliency_, eigenvalues_;
 };
 
+// pcl::MLSResult's projection methods (surface/include/pcl/surface/mls.h:68) and pcl::MovingLeastSquares<PointInT, PointOutT>
+// (mls.h:260-520, impl/mls.hpp:72-290) without upsampling, over pclhip_mls_process: polynomial orders 0 .. 2, the projection
+// methods NONE and SIMPLE; one output record per input point with at least 3 neighbours, in ascending index.  process()
+// leaves the output empty and says why in getLastError() for what this path does not build: the ORTHOGONAL projection,
+// order > 2, an upsampling method, setIndices, another search surface, cached MLS results, a foreign Search.
+struct MLSResult {
+  enum ProjectionMethod { NONE, SIMPLE, ORTHOGONAL };
+};
+
+template <typename PointInT, typename PointOutT>
+class MovingLeastSquares : public PCLBase<PointInT> {
+ public:
+  using KdTree = search::Search<PointInT>;
+  using KdTreePtr = typename KdTree::Ptr;
+  using PointCloudOut = PointCloud<PointOutT>;
+  enum UpsamplingMethod { NONE, DISTINCT_CLOUD, SAMPLE_LOCAL_PLANE, RANDOM_UNIFORM_DENSITY, VOXEL_GRID_DILATION };
+  MovingLeastSquares() : MovingLeastSquares(Context::defaultContext()) {}
+  explicit MovingLeastSquares(Context::Ptr ctx) : ctx_(std::move(ctx)) {}
+  void setSearchMethod(const KdTreePtr& tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setSearchRadius(double radius) { search_radius_ = radius; sqr_gauss_param_ = radius * radius; }  // mls.h:365
+  double getSearchRadius() const { return search_radius_; }
+  void setSqrGaussParam(double sqr_gauss_param) { sqr_gauss_param_ = sqr_gauss_param; }
+  double getSqrGaussParam() const { return sqr_gauss_param_; }
+  void setPolynomialOrder(int order) { order_ = order; }
+  int getPolynomialOrder() const { return order_; }
+  void setProjectionMethod(MLSResult::ProjectionMethod method) { projection_method_ = method; }
+  MLSResult::ProjectionMethod getProjectionMethod() const { return projection_method_; }
+  void setComputeNormals(bool compute_normals) { compute_normals_ = compute_normals; }
+  void setUpsamplingMethod(UpsamplingMethod method) { upsample_method_ = method; }
+  void setCacheMLSResults(bool cache_mls_results) { cache_mls_results_ = cache_mls_results; }
+  bool getCacheMLSResults() const { return cache_mls_results_; }
+  void setSearchSurface(const typename PointCloud<PointInT>::ConstPtr& cloud) { surface_ = cloud; }
+  void setNumberOfThreads(unsigned int threads = 1) { threads_ = threads; }  // only stored
+  PointIndices::Ptr getCorrespondingIndices() const { return corresponding_input_indices_; }
+  const std::string& getLastError() const { return error_; }
+  // per output record, after process(): the unrounded point (3), normal (3), curvature and the neighbour count
+  const std::vector<double>& getUnrounded() const { return unrounded_; }
+
+  void process(PointCloudOut& output) {  // impl/mls.hpp:72-160
+    output.points.clear();
+    output.width = 0;
+    output.height = 1;
+    output.is_dense = true;
+    corresponding_input_indices_ = std::make_shared<PointIndices>();
+    unrounded_.clear();
+    error_.clear();
+    const char* why = nullptr;
+    if (!this->input_) why = "no input cloud";
+    else if (!(search_radius_ > 0.0) || !(sqr_gauss_param_ > 0.0)) why = "invalid search radius or Gaussian parameter";  // :109
+    else if (order_ < 0 || order_ > 2) why = "polynomial orders 0, 1 and 2 are built";
+    else if (projection_method_ == MLSResult::ORTHOGONAL) why = "the ORTHOGONAL projection is not built";
+    else if (upsample_method_ != NONE) why = "upsampling is not built";
+    else if (cache_mls_results_) why = "cached MLS results are not built";
+    else if (this->indices_ && !this->fake_indices_) why = "setIndices is not built";
+    else if (surface_ && surface_ != this->input_) why = "a search surface other than the input is not built";
+    else if (!ctx_ || !ctx_->ok()) why = "no device";
+    if (why != nullptr) {
+      error_ = why;
+      return;
+    }
+    const auto& input = this->input_;
+    if (input->empty()) return;
+    if (!tree_) tree_ = std::make_shared<search::KdTree<PointInT>>(ctx_);
+    auto* dev = dynamic_cast<search::KdTree<PointInT>*>(tree_.get());
+    if (dev == nullptr) {
+      error_ = "the search method is not a pclhip::search::KdTree";
+      return;
+    }
+    if (dev->getInputCloud() != input || dev->handle() == nullptr) {
+      if (!dev->setInputCloud(input)) {
+        error_ = pclhip_last_error(ctx_->get());
+        return;
+      }
+    }
+    const std::size_t n = input->size();
+    const bool normals = compute_normals_ && has_normal_fields<PointOutT>();
+    std::vector<float> xyz(3 * n), nrm(normals ? 4 * n : 0);
+    Indices& idx = corresponding_input_indices_->indices;
+    idx.resize(n);
+    unrounded_.assign(8 * n, 0.0);
+    std::uint64_t k = 0;
+    if (pclhip_mls_process(dev->handle(), search_radius_, sqr_gauss_param_, order_, int(projection_method_), xyz.data(),
+                           normals ? nrm.data() : nullptr, idx.data(), n, &k, unrounded_.data()) != PCLHIP_OK) {
+      error_ = pclhip_last_error(dev->context()->get());
+      idx.clear();
+      unrounded_.clear();
+      return;
+    }
+    idx.resize(std::size_t(k));
+    unrounded_.resize(8 * std::size_t(k));
+    output.points.reserve(std::size_t(k));
+    for (std::size_t i = 0; i < std::size_t(k); ++i) {  // addProjectedPointNormal, impl/mls.hpp:258-283
+      PointOutT p{};
+      p.x = xyz[3 * i];
+      p.y = xyz[3 * i + 1];
+      p.z = xyz[3 * i + 2];
+      if (normals) set_normal(p, &nrm[4 * i]);
+      output.push_back(p);
+    }
+    output.height = 1;
+    output.is_dense = true;
+  }
+
+ private:
+  template <typename P> static typename std::enable_if<(sizeof(P) >= 48)>::type set_normal(P& p, const float* v) {
+    p.normal_x = v[0];
+    p.normal_y = v[1];
+    p.normal_z = v[2];
+    p.curvature = v[3];
+  }
+  template <typename P> static typename std::enable_if<(sizeof(P) < 48)>::type set_normal(P&, const float*) {}
+  Context::Ptr ctx_;
+  KdTreePtr tree_;
+  typename PointCloud<PointInT>::ConstPtr surface_;
+  double search_radius_ = 0.0;  // mls.h:297-313: the reference's defaults
+  double sqr_gauss_param_ = 0.0;
+  int order_ = 2;
+  MLSResult::ProjectionMethod projection_method_ = MLSResult::SIMPLE;
+  bool compute_normals_ = false;
+  UpsamplingMethod upsample_method_ = NONE;
+  bool cache_mls_results_ = false;  // (the reference's default is true: it keeps what getMLSResults hands out, not built here)
+  unsigned int threads_ = 1;
+  PointIndices::Ptr corresponding_input_indices_ = std::make_shared<PointIndices>();
+  std::vector<double> unrounded_;
+  std::string error_;
+};
+
 // ---- pcl::ModelCoefficients (common/include/pcl/ModelCoefficients.h; `values` only), the model and method constants
 // (sample_consensus/model_types.h:45-47, method_types.h:45) and pcl::SACSegmentation<PointT> (segmentation/include/pcl/
 // segmentation/sac_segmentation.h:77-330, impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC over

@@ -9,7 +9,7 @@ from .api import (Communicator, Context, CorrespondenceEstimation, Correspondenc
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,
-                  IterativeClosestPointWithNormals, KdTree, NormalDistributionsTransform, NormalEstimation,
+                  IterativeClosestPointWithNormals, KdTree, MovingLeastSquares, NormalDistributionsTransform, NormalEstimation,
                   RadiusOutlierRemoval, SACSegmentation, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

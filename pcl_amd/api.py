@@ -7,6 +7,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::NormalEstimation                                features/include/pcl/features/normal_3d.h:243-420
   pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
   pcl::ISSKeypoint3D                                   keypoints/include/pcl/keypoints/iss_3d.h
+  pcl::MovingLeastSquares (no upsampling)              surface/include/pcl/surface/mls.h
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
   pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
   pcl::SACSegmentation (planes, RANSAC)                segmentation/include/pcl/segmentation/sac_segmentation.h:77-330
@@ -2179,6 +2180,134 @@ class ISSKeypoint3D:
         if _is_torch(self.cloud):
             return self.cloud[self._indices.long()]
         return np.asarray(self.cloud)[self._indices]
+
+
+class MovingLeastSquares:
+    """pcl::MovingLeastSquares<PointInT, PointOutT> without upsampling (surface/include/pcl/surface/mls.h, impl/mls.hpp)
+    over pclhip_mls_process: polynomial orders 0 .. 2, the projection methods NONE and SIMPLE.  The input is an
+    (n, c >= 3) float32 cloud, numpy or a torch CUDA tensor; the outputs come back in the same kind of array, one record per
+    input point with at least 3 neighbours, in ascending input index."""
+    NONE, SIMPLE, ORTHOGONAL = 0, 1, 2                                    # MLSResult::ProjectionMethod
+    UPSAMPLING_NONE, DISTINCT_CLOUD, SAMPLE_LOCAL_PLANE, RANDOM_UNIFORM_DENSITY, VOXEL_GRID_DILATION = range(5)
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.tree = None
+        self.cloud = None
+        self.search_radius = 0.0       # mls.h:297-313: the reference's defaults
+        self.sqr_gauss_param = 0.0
+        self.order = 2
+        self.projection_method = self.SIMPLE
+        self.compute_normals = False
+        self._indices = None
+        self._double = None
+
+    def getClassName(self):
+        return "MovingLeastSquares"
+
+    def setInputCloud(self, cloud):
+        self.cloud = cloud
+
+    def getInputCloud(self):
+        return self.cloud
+
+    def setSearchMethod(self, tree):
+        """An index over the same whole, unscaled cloud (a KdTree another stage built) is reused as it is."""
+        self.tree = tree
+
+    def getSearchMethod(self):
+        return self.tree
+
+    def setSearchRadius(self, r):
+        """mls.h:365: also sets sqr_gauss_param = r * r."""
+        self.search_radius = float(r)
+        self.sqr_gauss_param = self.search_radius * self.search_radius
+
+    def getSearchRadius(self):
+        return self.search_radius
+
+    def setSqrGaussParam(self, s):
+        self.sqr_gauss_param = float(s)
+
+    def getSqrGaussParam(self):
+        return self.sqr_gauss_param
+
+    def setPolynomialOrder(self, order):
+        self.order = int(order)
+
+    def getPolynomialOrder(self):
+        return self.order
+
+    def setProjectionMethod(self, method):
+        self.projection_method = int(method)
+
+    def getProjectionMethod(self):
+        return self.projection_method
+
+    def setComputeNormals(self, compute_normals):
+        self.compute_normals = bool(compute_normals)
+
+    def setUpsamplingMethod(self, method):
+        if int(method) != self.UPSAMPLING_NONE:
+            raise NotImplementedError("MovingLeastSquares: upsampling is not built")
+
+    def setNumberOfThreads(self, n=0):
+        pass
+
+    def lastPassMs(self):
+        """GPU time (ms) of the plane kernel and of the fit kernel of the last process()."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self.lib.pclhip_index_last_mls_ms(self.tree.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def lastKernelMs(self):
+        return float(self.lib.pclhip_index_last_kernel_ms(self.tree.h))
+
+    def _run(self, want_double):
+        assert self.cloud is not None, "setInputCloud first"
+        if self.tree is None:
+            self.tree = KdTree(self.ctx)
+        if self.tree.h is None or self.tree._cloud_id != (id(self.cloud), None):
+            self.tree.setInputCloud(self.cloud)
+        n = self.tree.n_cloud
+        if _is_torch(self.cloud):
+            import torch
+
+            def make(shape, dtype):
+                t = torch.empty(shape, dtype={np.int32: torch.int32, np.float32: torch.float32,
+                                              np.float64: torch.float64}[dtype], device=self.cloud.device)
+                return t, C.c_void_p(t.data_ptr())
+        else:
+            def make(shape, dtype):
+                a = np.empty(shape, dtype)
+                return a, C.c_void_p(a.ctypes.data)
+        pts, pp = make((max(n, 1), 3), np.float32)
+        nrm, npp = make((max(n, 1), 4), np.float32) if self.compute_normals else (None, None)
+        idx, ip = make(max(n, 1), np.int32)
+        dbl, dp = make((max(n, 1), 8), np.float64) if want_double else (None, None)
+        k = C.c_uint64(0)
+        check(self.lib.pclhip_mls_process(self.tree.h, self.search_radius, self.sqr_gauss_param, self.order,
+                                          self.projection_method, pp, npp, ip, n, C.byref(k), dp), self.ctx.h)
+        k = int(k.value)
+        self._indices = idx[:k]
+        self._double = None if dbl is None else dbl[:k]
+        if nrm is None:
+            return pts[:k], None, None, self._indices
+        return pts[:k], nrm[:k, :3], nrm[:k, 3], self._indices
+
+    def process(self):
+        """-> (points float32 [k, 3], normals float32 [k, 3], curvature float32 [k], corresponding indices int32 [k]);
+        normals and curvature are None without setComputeNormals(True)."""
+        return self._run(False)
+
+    def processAll(self):
+        """process() and the unrounded records: float64 [k, 8] = point (3), normal (3), curvature, neighbour count."""
+        out = self._run(True)
+        return out + (self._double,)
+
+    def getCorrespondingIndices(self):
+        return self._indices
 
 
 class EuclideanClusterExtraction:

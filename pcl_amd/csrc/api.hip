@@ -1423,6 +1423,37 @@ void pclhip_index_last_iss_ms(const pclhip_index* ix, double* scatter_ms, double
   if (nms_ms) *nms_ms = ix ? ix->iss_pass_ms[1] : 0.0;
 }
 
+// ---- MovingLeastSquares (mls.hpp) ------------------------------------------------------------------
+pclhip_status pclhip_mls_process(pclhip_index* ix, double search_radius, double sqr_gauss_param, int polynomial_order,
+                                 int projection_method, float* out_points, float* out_normals, int32_t* out_indices,
+                                 uint64_t capacity, uint64_t* n_out, double* out_double) {
+  if (!ix || !n_out) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_out = 0;
+  // MovingLeastSquares::process (impl/mls.hpp:109-114) logs these and returns an empty output
+  PCLHIP_REQUIRE(ctx, std::isfinite(search_radius) && search_radius > 0.0, "the search radius must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, std::isfinite(sqr_gauss_param) && sqr_gauss_param > 0.0, "sqr_gauss_param must be finite and > 0");
+  PCLHIP_REQUIRE(ctx, polynomial_order >= 0 && polynomial_order <= 2, "MLS: polynomial orders 0, 1 and 2 are built");
+  PCLHIP_REQUIRE(ctx, projection_method != PCLHIP_MLS_ORTHOGONAL,
+                 "MLS: the ORTHOGONAL projection is not built (the reference's Newton loop has no iteration cap)");
+  PCLHIP_REQUIRE(ctx, projection_method == PCLHIP_MLS_NONE || projection_method == PCLHIP_MLS_SIMPLE,
+                 "MLS: unknown projection method");
+  if (ix->scaled || ix->subset) {
+    set_error(ctx, "MLS needs an index built over the whole cloud in its own coordinates (no indices, no rescaling)");
+    return PCLHIP_ERR_STATE;
+  }
+  // radiusSearch keeps d2 < float(r * r) (kdtree_flann.hpp:398)
+  return mls_process(ix, float(search_radius * search_radius), sqr_gauss_param,
+                     polynomial_order == 2 && projection_method == PCLHIP_MLS_SIMPLE, out_points, out_normals, out_indices,
+                     capacity, n_out, out_double);
+}
+
+void pclhip_index_last_mls_ms(const pclhip_index* ix, double* plane_ms, double* fit_ms) {
+  if (plane_ms) *plane_ms = ix ? ix->mls_pass_ms[0] : 0.0;
+  if (fit_ms) *fit_ms = ix ? ix->mls_pass_ms[1] : 0.0;
+}
+
 // ---- EuclideanClusterExtraction (cluster.hpp) ------------------------------------------------------
 pclhip_status pclhip_euclidean_clusters(pclhip_index* ix, double tolerance, uint32_t min_size, uint32_t max_size,
                                         int32_t* out_labels, uint64_t* out_offsets, uint64_t offsets_capacity,

@@ -437,6 +437,9 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // ISSKeypoint3D: two radius traversals of the index, scatter eigenvalues and non-maximum suppression
 #include "iss.hpp"
 
+// MovingLeastSquares: two radius traversals of the index, the plane's eigenpair and the polynomial's normal equations
+#include "mls.hpp"
+
 // EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
 #include "cluster.hpp"
 
