@@ -368,6 +368,44 @@ PCLHIP_API pclhip_status pclhip_mls_process(pclhip_index* index, double search_r
                                             double* out_double);
 /* GPU time (ms) of the plane kernel and of the fit kernel (0 when it did not run) of the last pclhip_mls_process. */
 PCLHIP_API void pclhip_index_last_mls_ms(const pclhip_index* index, double* plane_ms, double* fit_ms);
+/* pcl::BoundaryEstimation<PointInT, PointNT, PointOutT>::computeFeature and ::isBoundaryPoint (features/include/pcl/
+ * features/impl/boundary.hpp:87-137, 141-209; getCoordinateSystemOnPlane, boundary.h:161-168): search surface == input.
+ * `index` is built over the whole unscaled cloud and holds normals (pclhip_normals* or pclhip_index_set_normals).
+ * Per query q with normal n:
+ *   1. The neighbourhood: with radius > 0 every indexed point with float d2 < float(radius * radius), q included (as
+ *      pclhip_radius_search); with k >= 1 the k nearest, q included (the lists of pclhip_knn).  Fewer than
+ *      max(3, min_neighbors) entries: flag 0.
+ *   2. v = (nx, ny, nz, 0).unitOrthogonal() by Eigen's rule for 4-vectors (maxi the first index of the largest |component|,
+ *      sndi = maxi == 0 ? 1 : 0, v[maxi] = -n[sndi] * inv, v[sndi] = n[maxi] * inv, inv = 1 / sqrt(n[sndi]^2 + n[maxi]^2)),
+ *      u = n x v, in float.
+ *   3. Per neighbour p: delta = p - q in float, an all-zero delta (q itself, a duplicate) is skipped; the angle is
+ *      atan2f(v . delta, u . delta).  No angle left: flag 0.
+ *   4. flag = (the largest difference of consecutive sorted angles, the wrap-around 2 * float(pi) - last + first
+ *      included) > float(angle_threshold).
+ *   out_flags          (host or device) one byte per query, 0 or 1: every record of the cloud, or indices[0..n_indices) in
+ *                      that order (repeats allowed; an index out of range is PCLHIP_ERR_INVALID)
+ *   out_invalid_count  (optional) the queries without a defined feature, see the deviations
+ * Exactly one of radius > 0 and k >= 1 must be given: anything else is PCLHIP_ERR_INVALID, as is an angle_threshold that
+ * is not finite or below pi / 8.  min_neighbors < 3 acts as 3 (the reference's rule); a keypoint detector's edge pass is
+ * the same call with its own minimum.  An index without normals, or one built with `indices` or rescale values, is
+ * PCLHIP_ERR_STATE.  A positive radius whose float square is 0 is a valid call in which nobody has a neighbour: every flag
+ * is 0 and every query is counted invalid.
+ * The flag is the reference's wherever no gap lies within rounding of the threshold: the angles are computed with the
+ * reference's float operations and the decisive gap is the float difference of the same two angles; nothing is sorted and no
+ * neighbour list is kept (pcl_amd/csrc/boundary.hpp).  A flag depends on the set of angles only, so two calls give the same
+ * bytes.
+ * Deviations: a query with no neighbour, a non-finite query and a query whose normal is non-finite or zero get flag 0 and
+ * are counted in out_invalid_count (the reference stores quiet_NaN() cast to uint8_t and clears is_dense, or sorts NaN
+ * angles); non-finite records are never neighbours.  Not built: angle_threshold < pi / 8, another search surface, the
+ * border exclusion of ISSKeypoint3D (it is not wired to this call), a pcl_plugin.hpp class.
+ * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_boundary_ms that of its mask pass
+ * and of its resolve passes together (k mode: of its one kernel, and 0). */
+PCLHIP_API pclhip_status pclhip_boundary(pclhip_index* index, const int32_t* indices, uint64_t n_indices, double radius,
+                                         int k, double angle_threshold, int min_neighbors, uint8_t* out_flags,
+                                         uint64_t* out_invalid_count);
+PCLHIP_API void pclhip_index_last_boundary_ms(const pclhip_index* index, double* mask_ms, double* resolve_ms);
+/* How many queries of the last pclhip_boundary on this index the mask pass left to the resolve pass. */
+PCLHIP_API uint64_t pclhip_index_last_boundary_resolved(const pclhip_index* index);
 /* pcl::EuclideanClusterExtraction<PointT>::extract (segmentation/.../impl/extract_clusters.hpp:124-253): the clusters are
  * the connected components of the graph over the index's points with an edge wherever float d2 < float(r * r),
  * r = double(float(tolerance)) -- the relation of pclhip_radius_search.  The index defines the set of points: built with

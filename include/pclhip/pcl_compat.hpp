@@ -27,6 +27,7 @@
 // Errors follow PCL's convention: no exceptions on the hot path, `false`/0 results + a message (getLastError()).
 #pragma once
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <array>
@@ -630,6 +631,166 @@ class FPFHEstimationOMP : public FPFHEstimation<PointInT, PointNT, PointOutT> {
   unsigned int getNumberOfThreads() const { return threads_; }
  private:
   unsigned int threads_ = 0;
+};
+
+// pcl::Boundary (common/include/pcl/impl/point_types.hpp): one byte, 1 for a boundary point
+struct Boundary {
+  std::uint8_t boundary_point = 0;
+};
+static_assert(sizeof(Boundary) == 1, "pcl::Boundary: the flag is the record");
+
+// What the reference's boundary code uses of Eigen::Vector4f: four floats, Zero(), coefficient access and dot().
+struct Vector4f {
+  float v[4] = {0, 0, 0, 0};
+  Vector4f() = default;
+  Vector4f(float a, float b, float c, float d) : v{a, b, c, d} {}
+  static Vector4f Zero() { return Vector4f(); }
+  float& operator[](int i) { return v[i]; }
+  float operator[](int i) const { return v[i]; }
+  float dot(const Vector4f& o) const { return ((v[0] * o.v[0] + v[1] * o.v[1]) + v[2] * o.v[2]) + v[3] * o.v[3]; }
+};
+template <typename PointNT>
+inline Vector4f getNormalVector4f(const PointNT& p) { return Vector4f(p.normal_x, p.normal_y, p.normal_z, 0.0f); }
+
+// pcl::BoundaryEstimation<PointInT, PointNT, PointOutT> (features/include/pcl/features/boundary.h:79-178, impl/boundary.hpp
+// :87-209) over pclhip_boundary, by radius or by k.  getCoordinateSystemOnPlane and isBoundaryPoint are the reference's host
+// functions restated (Eigen's unitOrthogonal rule for 4-vectors written out; the angles sorted on the host).  compute()
+// leaves the output empty and says why in getLastError() for what this path does not build: another search surface, a
+// foreign Search, an angle threshold below pi / 8.  PointNT is pcl::Normal or pcl::PointNormal.
+template <typename PointInT, typename PointNT, typename PointOutT = Boundary>
+class BoundaryEstimation : public PCLBase<PointInT> {
+  static_assert(sizeof(PointOutT) == 1, "the output type is pcl::Boundary");
+ public:
+  using SearchPtr = typename search::Search<PointInT>::Ptr;
+  using PointCloudOut = PointCloud<PointOutT>;
+  using PointCloudNConstPtr = typename PointCloud<PointNT>::ConstPtr;
+  BoundaryEstimation() : BoundaryEstimation(Context::defaultContext()) {}
+  explicit BoundaryEstimation(Context::Ptr ctx) : ctx_(std::move(ctx)) {}
+  virtual ~BoundaryEstimation() = default;
+  void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setSearchMethod(const SearchPtr& tree) { tree_ = tree; }
+  SearchPtr getSearchMethod() const { return tree_; }
+  void setSearchSurface(const typename PointCloud<PointInT>::ConstPtr& cloud) { surface_ = cloud; }
+  typename PointCloud<PointInT>::ConstPtr getSearchSurface() const { return surface_; }
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double radius) { radius_ = radius; }
+  double getRadiusSearch() const { return radius_; }
+  double getSearchParameter() const { return k_ >= 1 ? double(k_) : radius_; }
+  void setAngleThreshold(float angle) { angle_threshold_ = angle; }  // boundary.h:131-141
+  float getAngleThreshold() const { return angle_threshold_; }
+  void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }  // only stored
+  unsigned int getNumberOfThreads() const { return threads_; }
+  std::uint64_t getInvalidCount() const { return invalid_; }
+  const std::string& getLastError() const { return error_; }
+
+  // boundary.h:161-168
+  void getCoordinateSystemOnPlane(const PointNT& p_coeff, Vector4f& u, Vector4f& v) const {
+    const Vector4f n = getNormalVector4f(p_coeff);
+    int maxi = 0;  // the first index of the largest |coefficient|
+    for (int i = 1; i < 4; ++i)
+      if (std::fabs(n[i]) > std::fabs(n[maxi])) maxi = i;
+    const int sndi = maxi == 0 ? 1 : 0;
+    const float inv = 1.0f / std::sqrt(n[sndi] * n[sndi] + n[maxi] * n[maxi]);
+    v = Vector4f::Zero();
+    v[maxi] = -n[sndi] * inv;
+    v[sndi] = n[maxi] * inv;
+    u = Vector4f(n[1] * v[2] - n[2] * v[1], n[2] * v[0] - n[0] * v[2], n[0] * v[1] - n[1] * v[0], 0.0f);
+  }
+  // impl/boundary.hpp:72-84, 87-137
+  bool isBoundaryPoint(const PointCloud<PointInT>& cloud, int q_idx, const Indices& indices, const Vector4f& u,
+                       const Vector4f& v, float angle_threshold) const {
+    return isBoundaryPoint(cloud, cloud[std::size_t(q_idx)], indices, u, v, angle_threshold);
+  }
+  bool isBoundaryPoint(const PointCloud<PointInT>& cloud, const PointInT& q_point, const Indices& indices, const Vector4f& u,
+                       const Vector4f& v, float angle_threshold) const {
+    if (indices.size() < 3) return false;
+    if (!std::isfinite(q_point.x) || !std::isfinite(q_point.y) || !std::isfinite(q_point.z)) return false;
+    std::vector<float> angles;
+    angles.reserve(indices.size());
+    for (const index_t i : indices) {
+      const PointInT& p = cloud[std::size_t(i)];
+      if (!std::isfinite(p.x) || !std::isfinite(p.y) || !std::isfinite(p.z)) continue;
+      const Vector4f delta(p.x - q_point.x, p.y - q_point.y, p.z - q_point.z, 0.0f);
+      if (delta[0] == 0.0f && delta[1] == 0.0f && delta[2] == 0.0f) continue;
+      angles.push_back(std::atan2(v.dot(delta), u.dot(delta)));
+    }
+    if (angles.empty()) return false;
+    std::sort(angles.begin(), angles.end());
+    float max_dif = 0.0f;
+    for (std::size_t i = 0; i + 1 < angles.size(); ++i) max_dif = std::max(max_dif, angles[i + 1] - angles[i]);
+    max_dif = std::max(max_dif, 2 * static_cast<float>(M_PI) - angles.back() + angles.front());
+    return max_dif > angle_threshold;
+  }
+
+  // Feature::compute (impl/feature.hpp:195-229)
+  void compute(PointCloudOut& output) {
+    output.points.clear();
+    output.is_dense = true;
+    error_.clear();
+    invalid_ = 0;
+    const char* why = nullptr;
+    const auto& input = this->input_;
+    if (!input) why = "no input cloud";
+    else if (!normals_ || normals_->size() != input->size()) why = "the normals do not match the input cloud";  // feature.hpp:241-250
+    else if ((k_ >= 1) == (radius_ > 0.0)) why = "exactly one of setKSearch and setRadiusSearch must be given";  // :131-174
+    else if (surface_ && surface_ != input) why = "a search surface other than the input is not built";
+    else if (!ctx_ || !ctx_->ok()) why = "no device";
+    if (why != nullptr) {
+      error_ = why;
+      return;
+    }
+    computeFeature(output);
+  }
+
+ protected:
+  virtual void computeFeature(PointCloudOut& output) {
+    const auto& input = this->input_;
+    if (!tree_) tree_ = std::make_shared<search::KdTree<PointInT>>(ctx_);
+    auto* dev = dynamic_cast<search::KdTree<PointInT>*>(tree_.get());
+    if (dev == nullptr) {
+      error_ = "the search method is not a pclhip::search::KdTree";
+      return;
+    }
+    if (dev->getInputCloud() != input || dev->handle() == nullptr) {
+      if (!dev->setInputCloud(input)) {
+        error_ = pclhip_last_error(ctx_->get());
+        return;
+      }
+    }
+    if (input->size() > 0 &&
+        pclhip_index_set_normals(dev->handle(), &normals_->points[0].normal_x, sizeof(PointNT)) != PCLHIP_OK) {
+      error_ = pclhip_last_error(dev->context()->get());
+      return;
+    }
+    const bool subset = this->indices_ && !this->fake_indices_;
+    const std::size_t m = subset ? this->indices_->size() : input->size();
+    output.resize(m);
+    output.height = 1;
+    if (m == 0) return;
+    if (pclhip_boundary(dev->handle(), subset ? this->indices_->data() : nullptr, subset ? m : 0, k_ >= 1 ? 0.0 : radius_,
+                        k_ >= 1 ? k_ : 0, double(angle_threshold_), 3,
+                        m > 0 ? reinterpret_cast<std::uint8_t*>(output.points.data()) : nullptr, &invalid_) != PCLHIP_OK) {
+      error_ = pclhip_last_error(dev->context()->get());
+      output.points.clear();
+      return;
+    }
+    output.height = 1;
+    output.is_dense = (invalid_ == 0);  // impl/boundary.hpp:164-177, 190-203
+  }
+
+ private:
+  Context::Ptr ctx_;
+  SearchPtr tree_;
+  typename PointCloud<PointInT>::ConstPtr surface_;
+  PointCloudNConstPtr normals_;
+  int k_ = 0;
+  double radius_ = 0.0;
+  float angle_threshold_ = static_cast<float>(M_PI) / 2.0f;  // boundary.h:91
+  unsigned int threads_ = 0;
+  std::uint64_t invalid_ = 0;
+  std::string error_;
 };
 
 namespace registration {

@@ -5,7 +5,7 @@ bench.py.  The C++ mirror of the same surface is include/pclhip/pcl_compat.hpp."
 from . import synth  # noqa: F401
 from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_PLANE, SYMMETRIC, PclHipError,  # noqa: F401
                    PclHipUnavailable)
-from .api import (Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
+from .api import (BoundaryEstimation, Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,

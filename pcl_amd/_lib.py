@@ -276,6 +276,9 @@ SIGNATURES = {
     "pclhip_mls_process": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _u64, C.POINTER(_u64),
                                      _vp]),
     "pclhip_index_last_mls_ms": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pclhip_boundary": (C.c_int, [_vp, _vp, _u64, C.c_double, C.c_int, C.c_double, C.c_int, _vp, C.POINTER(_u64)]),
+    "pclhip_index_last_boundary_ms": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pclhip_index_last_boundary_resolved": (_u64, [_vp]),
     "pclhip_euclidean_clusters": (C.c_int, [_vp, C.c_double, C.c_uint32, C.c_uint32, _vp, C.POINTER(_u64), _u64, _vp, _u64,
                                             C.POINTER(_u64), C.POINTER(_u64)]),
     "pclhip_index_last_cluster_stats": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_u64)]),

@@ -8,6 +8,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::FPFHEstimation                                  features/include/pcl/features/fpfh.h:79-222
   pcl::ISSKeypoint3D                                   keypoints/include/pcl/keypoints/iss_3d.h
   pcl::MovingLeastSquares (no upsampling)              surface/include/pcl/surface/mls.h
+  pcl::BoundaryEstimation                              features/include/pcl/features/boundary.h
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
   pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
   pcl::SACSegmentation (planes, RANSAC)                segmentation/include/pcl/segmentation/sac_segmentation.h:77-330
@@ -2180,6 +2181,116 @@ class ISSKeypoint3D:
         if _is_torch(self.cloud):
             return self.cloud[self._indices.long()]
         return np.asarray(self.cloud)[self._indices]
+
+
+class BoundaryEstimation:
+    """pcl::BoundaryEstimation<PointInT, PointNT, pcl::Boundary> (features/include/pcl/features/boundary.h, impl/
+    boundary.hpp:87-209) over pclhip_boundary: search surface == input, by radius or by k.  The normals are the ones given
+    with setInputNormals, or the ones the tree already holds.  The input is an (n, c >= 3) float32 cloud, numpy or a torch
+    CUDA tensor; the flags come back as uint8 in the same kind of array, one per query."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.tree = None
+        self.radius = 0.0
+        self.k = 0
+        self.angle_threshold = math.pi / 2.0   # boundary.h:91: the reference's default
+        self.min_neighbors = 3
+        self.cloud = None
+        self.normals = None
+        self.indices = None
+        self.invalid_count = 0
+
+    def getClassName(self):
+        return "BoundaryEstimation"
+
+    def setInputCloud(self, cloud):
+        self.cloud = cloud
+
+    def getInputCloud(self):
+        return self.cloud
+
+    def setInputNormals(self, normals):
+        """FeatureFromNormals::setInputNormals: one normal per record of the input cloud, (n, c >= 3)."""
+        self.normals = normals
+
+    def getInputNormals(self):
+        return self.normals
+
+    def setSearchMethod(self, tree):
+        self.tree = tree
+
+    def getSearchMethod(self):
+        return self.tree
+
+    def setIndices(self, indices):
+        """PCLBase::setIndices: one flag per input[indices[j]], in that order (None: every record)."""
+        self.indices = None if indices is None else np.ascontiguousarray(indices, np.int32)
+
+    def setRadiusSearch(self, radius):
+        self.radius = float(radius)
+
+    def getRadiusSearch(self):
+        return self.radius
+
+    def setKSearch(self, k):
+        self.k = int(k)
+
+    def getKSearch(self):
+        return self.k
+
+    def setAngleThreshold(self, angle):
+        self.angle_threshold = float(angle)
+
+    def getAngleThreshold(self):
+        return self.angle_threshold
+
+    def setNumberOfThreads(self, n=0):
+        pass
+
+    def lastPassMs(self):
+        """GPU time (ms) of the mask pass and of the resolve passes of the last compute()."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self.lib.pclhip_index_last_boundary_ms(self.tree.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def lastResolved(self):
+        """How many queries of the last compute() the mask pass left to the resolve pass."""
+        return int(self.lib.pclhip_index_last_boundary_resolved(self.tree.h))
+
+    def lastKernelMs(self):
+        return float(self.lib.pclhip_index_last_kernel_ms(self.tree.h))
+
+    def compute(self):
+        """-> uint8 [m]: 1 for a boundary point; the queries without a defined feature are counted in invalid_count."""
+        assert self.cloud is not None, "setInputCloud first"
+        if self.tree is None:
+            self.tree = KdTree(self.ctx)
+        if self.tree.h is None or self.tree._cloud_id != (id(self.cloud), None):
+            self.tree.setInputCloud(self.cloud)
+        if self.normals is not None:
+            self.tree.setNormals(self.normals)
+        n = self.tree.n_cloud
+        m = n if self.indices is None else len(self.indices)
+        if _is_torch(self.cloud):
+            import torch
+            out = torch.empty(m, dtype=torch.uint8, device=self.cloud.device)
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty(m, np.uint8)
+            optr = C.c_void_p(out.ctypes.data)
+        bad = C.c_uint64(0)
+        none = np.zeros(1, np.int32)
+        if self.indices is None:
+            ind, ni = None, 0
+        else:  # (an empty list is a list: no query)
+            ind, ni = C.c_void_p((self.indices if m > 0 else none).ctypes.data), m
+        self.invalid_count = 0
+        check(self.lib.pclhip_boundary(self.tree.h, ind, ni, self.radius, self.k, self.angle_threshold, self.min_neighbors,
+                                       optr, C.byref(bad)), self.ctx.h)
+        self.invalid_count = int(bad.value)
+        return out
 
 
 class MovingLeastSquares:

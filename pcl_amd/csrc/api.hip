@@ -1454,6 +1454,42 @@ void pclhip_index_last_mls_ms(const pclhip_index* ix, double* plane_ms, double* 
   if (fit_ms) *fit_ms = ix ? ix->mls_pass_ms[1] : 0.0;
 }
 
+// ---- BoundaryEstimation (boundary.hpp) ---------------------------------------------------------------
+pclhip_status pclhip_boundary(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, double radius, int k,
+                              double angle_threshold, int min_neighbors, uint8_t* out_flags, uint64_t* out_invalid_count) {
+  if (!ix) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  if (out_invalid_count) *out_invalid_count = 0;
+  const bool by_radius = radius > 0.0, by_k = k >= 1;  // (a NaN radius is no radius)
+  PCLHIP_REQUIRE(ctx, by_radius != by_k, "exactly one of radius > 0 and k >= 1 selects the neighbourhood");
+  PCLHIP_REQUIRE(ctx, !by_radius || std::isfinite(radius), "the radius must be finite");
+  PCLHIP_REQUIRE(ctx, std::isfinite(angle_threshold) && angle_threshold >= 0.39269908169872414,
+                 "the angle threshold must be finite and >= pi / 8 (smaller ones are not built)");
+  PCLHIP_REQUIRE(ctx, indices != nullptr || n_indices == 0, "null indices");
+  const uint64_t m = indices ? n_indices : ix->n_orig;
+  PCLHIP_REQUIRE(ctx, out_flags != nullptr || m == 0, "null buffer");
+  if (ix->scaled || ix->subset) {
+    set_error(ctx, "boundary estimation needs an index built over the whole cloud in its own coordinates (no indices, no rescaling)");
+    return PCLHIP_ERR_STATE;
+  }
+  if (!ix->has_normals) {
+    set_error(ctx, "boundary estimation needs normals in the index: pclhip_normals* or pclhip_index_set_normals first");
+    return PCLHIP_ERR_STATE;
+  }
+  // radiusSearch keeps d2 < float(r * r) (kdtree_flann.hpp:398); max_dif > angle_threshold is a comparison of floats
+  return boundary_compute(ix, indices, n_indices, by_radius ? float(radius * radius) : 0.0f, by_radius ? 0 : k,
+                          float(angle_threshold), uint32_t(min_neighbors < 3 ? 3 : min_neighbors), out_flags,
+                          out_invalid_count);
+}
+
+void pclhip_index_last_boundary_ms(const pclhip_index* ix, double* mask_ms, double* resolve_ms) {
+  if (mask_ms) *mask_ms = ix ? ix->boundary_pass_ms[0] : 0.0;
+  if (resolve_ms) *resolve_ms = ix ? ix->boundary_pass_ms[1] : 0.0;
+}
+
+uint64_t pclhip_index_last_boundary_resolved(const pclhip_index* ix) { return ix ? ix->boundary_pending : 0; }
+
 // ---- EuclideanClusterExtraction (cluster.hpp) ------------------------------------------------------
 pclhip_status pclhip_euclidean_clusters(pclhip_index* ix, double tolerance, uint32_t min_size, uint32_t max_size,
                                         int32_t* out_labels, uint64_t* out_offsets, uint64_t offsets_capacity,

@@ -301,6 +301,8 @@ struct pclhip_index {
   double fpfh_pass_ms[2] = {0, 0};  // the SPFH and the weighting kernel of the last pclhip_fpfh
   double iss_pass_ms[2] = {0, 0};   // the scatter and the non-max kernel of the last pclhip_iss_keypoints
   double mls_pass_ms[2] = {0, 0};   // the plane and the fit kernel of the last pclhip_mls_process
+  double boundary_pass_ms[2] = {0, 0};  // the mask kernel and the resolve kernels of the last pclhip_boundary
+  uint64_t boundary_pending = 0;    // ... and the queries its mask pass left to the resolve pass
   double cluster_ms[2] = {0, 0};    // the hook and the flatten kernel of the last pclhip_euclidean_clusters
   uint64_t cluster_unions = 0;      // ... and the unions its hook kernel attempted
   bool has_normals = false;
@@ -598,6 +600,10 @@ pclhip_status iss_keypoints(pclhip_index* ix, float t_sal, float t_nms, double g
 // whether the polynomial pass runs
 pclhip_status mls_process(pclhip_index* ix, float t, double sqr_gauss_param, bool fit, float* out_points, float* out_normals,
                           int32_t* out_indices, uint64_t capacity, uint64_t* n_out, double* out_double);
+// BoundaryEstimation over the index (boundary.hpp, compiled into radius.hip): t is the float square of the radius (k == 0),
+// or k >= 1 neighbours; min_nb below 3 acts as 3
+pclhip_status boundary_compute(pclhip_index* ix, const int32_t* indices, uint64_t n_indices, float t, int k, float thr,
+                               uint32_t min_nb, uint8_t* out_flags, uint64_t* out_invalid);
 // EuclideanClusterExtraction over the index (cluster.hpp, compiled into radius.hip): the components of d2 < t
 pclhip_status euclidean_clusters(pclhip_index* ix, float t, uint32_t min_size, uint32_t max_size, int32_t* out_labels,
                                  uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices,

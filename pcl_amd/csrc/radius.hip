@@ -440,6 +440,9 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // MovingLeastSquares: two radius traversals of the index, the plane's eigenpair and the polynomial's normal equations
 #include "mls.hpp"
 
+// BoundaryEstimation: a radius traversal that fills an angle occupancy mask, a second one for the gaps the mask leaves open
+#include "boundary.hpp"
+
 // EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
 #include "cluster.hpp"
 
