@@ -1025,7 +1025,8 @@ PCLHIP_API void pclhip_scp_last_ms(const pclhip_scp* scp, double* knn_ms, double
  * inside getSamples first); the norm is a plain sqrtf (Eigen's stableNorm guards an underflow the 1e-5 test makes moot);
  * one distance expression and float(threshold) everywhere (selectWithinDistance uses Eigen's dot and compares a float with
  * a double); the refit's double tree sums replace a sequential float sum.
- * Not built: other models and methods, setSamplesMaxDist, multi-GPU. */
+ * Not built: models that are not planes (the constrained and the normal plane models follow below), other methods,
+ * setSamplesMaxDist, multi-GPU. */
 typedef struct {
   double distance_threshold;        /* sac_segmentation.h:90, default 0.0 */
   int max_iterations;               /* default 50 */
@@ -1067,6 +1068,81 @@ PCLHIP_API pclhip_status pclhip_sac_plane_evaluate(pclhip_ctx* ctx, const void* 
  * first min(capacity, *count) records to buf (host). */
 PCLHIP_API pclhip_status pclhip_sac_last_trace(pclhip_ctx* ctx, pclhip_sac_plane_trace* buf, uint64_t capacity,
                                                uint64_t* count);
+
+/* ---- SACSegmentation: the constrained planes and SACSegmentationFromNormals ----------------------------
+ * The plane models with a gate per hypothesis (sample_consensus/.../impl/sac_model_perpendicular_plane.hpp:93-119,
+ * sac_model_parallel_plane.hpp:92-115, sac_model_normal_parallel_plane.hpp:48-78) and the plane scored with the points'
+ * normals (impl/sac_model_normal_plane.hpp:48-101,128-162: the standard path), as pcl::SACSegmentation and
+ * pcl::SACSegmentationFromNormals reach them (segmentation/.../impl/sac_segmentation.hpp:230-262,374-531).  Samples,
+ * coefficients, the replay, the refit and the lists are those of the plane above; model 0 gives the bytes of
+ * pclhip_sac_segment_plane.
+ * Float sums of three terms have ONE order here: dot3(u, v) = (u.x v.x + u.z v.z) + u.y v.y, what a 4-lane packet
+ * reduction of a Vector4f with w = 0 produces; no contraction.  normalized(v) = v / sqrtf(dot3(v, v)) when that squared
+ * norm is > 0, else v itself (Eigen's normalized()).  angle(u, v) = acos(clamp(double(dot3(normalized(u), normalized(v))),
+ * -1, 1)) in double, folded: a = min(a, M_PI - a) as std::min does (M_PI - a when that is smaller).
+ * The gate of a hypothesis (a, b, c, d), n = (a, b, c); with eps_angle > 0 only:
+ *   PERPENDICULAR_PLANE (9)         invalid when angle(axis, n) > eps_angle
+ *   PARALLEL_PLANE (15)             invalid when double(fabsf(dot3(axis, normalized(n)))) > |sin(eps_angle)|
+ *   NORMAL_PARALLEL_PLANE (16)      invalid when double(fabsf(dot3(axis, normalized(n)))) < |cos(eps_angle)|; and with
+ *                                   eps_dist > 0: invalid when fabs(double(-d) - distance_from_origin) > eps_dist
+ * (sin and cos are the host's).  A comparison with a NaN is false: such a hypothesis passes the gate and counts 0.
+ * An invalid hypothesis is not a skipped trial: it is an iteration whose count is 0 (trace: skipped 0, valid 0).
+ * Models 9 and 15 score with the plane's expression.  Models 11 and 16 score a point p with normal record (nx, ny, nz,
+ * curvature) as
+ *   d_euclid = double(fabsf(dot3(n, p) + d)),  d_normal = angle((nx, ny, nz), n),
+ *   weight = normal_distance_weight * (1.0 - double(curvature)),
+ *   inlier iff fabs(weight * d_normal + (1.0 - weight) * d_euclid) < distance_threshold        (all in double)
+ * in counting and in both selections.  A NaN in the normal or the curvature gives a NaN distance: never an inlier.  The
+ * scoring pass decides most pairs without the angle (bounds that rounding cannot cross, sac_models.hpp); its flags are
+ * those of this expression with the device's double acos.  After the refit the refined coefficients pass the gate again:
+ * when they fail it the inlier list is EMPTY and the coefficients stay the refined ones (sac_segmentation.hpp:117-125).
+ * Refused (PCLHIP_ERR_INVALID with a message): a model type other than 0, 9, 11, 15, 16; models 11 and 16 without
+ * normals; a zero axis with eps_angle > 0 for models 9, 15, 16.
+ * Deviations, beyond the plane's: the double acos is the device's (the host's differs from it by ulps); the class never
+ * sets an eps_dist (sac_segmentation.hpp:440-468), this interface does. */
+enum {
+  PCLHIP_SACMODEL_PLANE = 0,                   /* sample_consensus/model_types.h:47-65 */
+  PCLHIP_SACMODEL_PERPENDICULAR_PLANE = 9,
+  PCLHIP_SACMODEL_NORMAL_PLANE = 11,
+  PCLHIP_SACMODEL_PARALLEL_PLANE = 15,
+  PCLHIP_SACMODEL_NORMAL_PARALLEL_PLANE = 16
+};
+typedef struct {
+  int model_type;                   /* default 0 */
+  float axis[3];                    /* default 0, 0, 0 */
+  double eps_angle;                 /* radians; <= 0 (default 0): no angle gate */
+  double normal_distance_weight;    /* setNormalDistanceWeight, default 0.1 */
+  double distance_from_origin;      /* model 16, default 0 */
+  double eps_dist;                  /* model 16; <= 0 (default 0): no distance gate */
+} pclhip_sac_model_params;
+typedef struct {                    /* pclhip_sac_plane_trace and the gate's bit */
+  int samples[3];
+  int skipped;
+  float coefficients[4];
+  uint32_t count;                   /* 0 for a skipped and for an invalid trial */
+  int valid;                        /* 0: skipped, or the hypothesis failed its gate */
+} pclhip_sac_model_trace;
+PCLHIP_API void pclhip_sac_model_params_default(pclhip_sac_model_params* p);
+/* pclhip_sac_segment_plane for any of the five models.  normals: n records (nx, ny, nz, curvature) of
+ * normals_stride_bytes (>= 16, a multiple of 4), host or device, read at the cloud's indices; null for models 0, 9, 15. */
+PCLHIP_API pclhip_status pclhip_sac_segment_model(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                  const void* normals, size_t normals_stride_bytes,
+                                                  const int32_t* indices, uint64_t n_indices,
+                                                  const pclhip_sac_plane_params* params,
+                                                  const pclhip_sac_model_params* model, float out_coeff[4],
+                                                  int32_t* out_inliers, uint64_t inliers_capacity, uint64_t* out_n_inliers,
+                                                  int32_t* out_outliers, uint64_t outliers_capacity,
+                                                  uint64_t* out_n_outliers, pclhip_sac_plane_stats* out_stats);
+/* countWithinDistance of the model for n_models coefficient quadruples (host): out_counts[m] (host; 0 for an invalid
+ * hypothesis), out_valid[m] (host, optional) the gate's bit (exposed for tests). */
+PCLHIP_API pclhip_status pclhip_sac_model_evaluate(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                   const void* normals, size_t normals_stride_bytes,
+                                                   const int32_t* indices, uint64_t n_indices, double threshold,
+                                                   const pclhip_sac_model_params* model, const float* coeffs,
+                                                   int n_models, uint32_t* out_counts, uint8_t* out_valid);
+/* pclhip_sac_last_trace with the gate's bit, for the last segment call of either kind of this context. */
+PCLHIP_API pclhip_status pclhip_sac_last_model_trace(pclhip_ctx* ctx, pclhip_sac_model_trace* buf, uint64_t capacity,
+                                                     uint64_t* count);
 
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/

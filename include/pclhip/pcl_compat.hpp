@@ -2380,23 +2380,47 @@ class MovingLeastSquares : public PCLBase<PointInT> {
 
 // ---- pcl::ModelCoefficients (common/include/pcl/ModelCoefficients.h; `values` only), the model and method constants
 // (sample_consensus/model_types.h:45-47, method_types.h:45) and pcl::SACSegmentation<PointT> (segmentation/include/pcl/
-// segmentation/sac_segmentation.h:77-330, impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC over
-// pclhip_sac_segment_plane.  Any other model or method leaves both outputs empty and says so in getLastError().
+// segmentation/sac_segmentation.h:77-330, impl/sac_segmentation.hpp:79-133,230-262) for SACMODEL_PLANE,
+// SACMODEL_PERPENDICULAR_PLANE and SACMODEL_PARALLEL_PLANE under SAC_RANSAC over pclhip_sac_segment_plane and
+// pclhip_sac_segment_model.  Any other model or method leaves both outputs empty and says so in getLastError().
 struct ModelCoefficients {
   using Ptr = std::shared_ptr<ModelCoefficients>;
   using ConstPtr = std::shared_ptr<const ModelCoefficients>;
   std::vector<float> values;
 };
-enum SacModel { SACMODEL_PLANE = 0 };
+enum SacModel {
+  SACMODEL_PLANE = 0,
+  SACMODEL_PERPENDICULAR_PLANE = 9,
+  SACMODEL_NORMAL_PLANE = 11,
+  SACMODEL_PARALLEL_PLANE = 15,
+  SACMODEL_NORMAL_PARALLEL_PLANE = 16
+};
 constexpr int SAC_RANSAC = 0;
+// What setAxis uses of Eigen::Vector3f: three floats.
+struct Vector3f {
+  float v[3] = {0, 0, 0};
+  Vector3f() = default;
+  Vector3f(float a, float b, float c) : v{a, b, c} {}
+  static Vector3f Zero() { return Vector3f(); }
+  float& operator[](int i) { return v[i]; }
+  float operator[](int i) const { return v[i]; }
+};
 
 template <typename PointT>
 class SACSegmentation : public PCLBase<PointT> {
  public:
   SACSegmentation() : SACSegmentation(Context::defaultContext()) {}
-  explicit SACSegmentation(Context::Ptr ctx) : ctx_(std::move(ctx)) { pclhip_sac_plane_params_default(&params_); }
+  explicit SACSegmentation(Context::Ptr ctx) : ctx_(std::move(ctx)) {
+    pclhip_sac_plane_params_default(&params_);
+    pclhip_sac_model_params_default(&model_);
+  }
   void setModelType(int model) { model_type_ = model; }
   int getModelType() const { return model_type_; }
+  // the axis and the largest angle to it (radians; 0: no constraint) of the constrained planes
+  void setAxis(const Vector3f& ax) { for (int i = 0; i < 3; ++i) model_.axis[i] = ax[i]; }
+  Vector3f getAxis() const { return Vector3f(model_.axis[0], model_.axis[1], model_.axis[2]); }
+  void setEpsAngle(double ea) { model_.eps_angle = ea; }
+  double getEpsAngle() const { return model_.eps_angle; }
   void setMethodType(int method) { method_type_ = method; }
   int getMethodType() const { return method_type_; }
   void setDistanceThreshold(double threshold) { params_.distance_threshold = threshold; }
@@ -2422,20 +2446,31 @@ class SACSegmentation : public PCLBase<PointT> {
     error_.clear();
     stats_ = pclhip_sac_plane_stats();
     stats_.best_trial = -1;
-    if (model_type_ != SACMODEL_PLANE || method_type_ != SAC_RANSAC) {
-      error_ = "SACSegmentation: only SACMODEL_PLANE with SAC_RANSAC is built";
+    if (!builds(model_type_) || method_type_ != SAC_RANSAC) {
+      error_ = getClassName() + ": only the plane models of this class with SAC_RANSAC are built";
       return;
     }
     if (!this->input_ || this->input_->empty() || !ctx_ || !ctx_->ok()) return;
     const bool subset = this->indices_ && !this->fake_indices_;
     if (subset && this->indices_->empty()) return;
     const std::size_t n = this->input_->size(), m = subset ? this->indices_->size() : n;
+    std::vector<float> normals;  // (nx, ny, nz, curvature) records, one per point
+    if (!normalRecords(n, normals)) return;
     Indices in(m), out(m);
     float coeff[4] = {0, 0, 0, 0};
     std::uint64_t n_in = 0, n_out = 0;
-    if (pclhip_sac_segment_plane(ctx_->get(), this->input_->points.data(), n, sizeof(PointT),
-                                 subset ? this->indices_->data() : nullptr, subset ? m : 0, &params_, coeff, in.data(), m, &n_in,
-                                 out.data(), m, &n_out, &stats_) != PCLHIP_OK) {
+    pclhip_status rc;
+    if (model_type_ == SACMODEL_PLANE && normals.empty()) {
+      rc = pclhip_sac_segment_plane(ctx_->get(), this->input_->points.data(), n, sizeof(PointT),
+                                    subset ? this->indices_->data() : nullptr, subset ? m : 0, &params_, coeff, in.data(), m,
+                                    &n_in, out.data(), m, &n_out, &stats_);
+    } else {
+      model_.model_type = model_type_;
+      rc = pclhip_sac_segment_model(ctx_->get(), this->input_->points.data(), n, sizeof(PointT),
+                                    normals.empty() ? nullptr : normals.data(), 16, subset ? this->indices_->data() : nullptr,
+                                    subset ? m : 0, &params_, &model_, coeff, in.data(), m, &n_in, out.data(), m, &n_out, &stats_);
+    }
+    if (rc != PCLHIP_OK) {
       error_ = pclhip_last_error(ctx_->get());
       return;
     }
@@ -2447,14 +2482,62 @@ class SACSegmentation : public PCLBase<PointT> {
     model_coefficients.values.assign(coeff, coeff + 4);
   }
 
- private:
+ protected:
+  virtual std::string getClassName() const { return "SACSegmentation"; }
+  // the models initSACModel builds (impl/sac_segmentation.hpp:136-370: none with normals)
+  virtual bool builds(int model) const {
+    return model == SACMODEL_PLANE || model == SACMODEL_PERPENDICULAR_PLANE || model == SACMODEL_PARALLEL_PLANE;
+  }
+  // the normals of the call as contiguous records; false: refuse the call (error_ says why)
+  virtual bool normalRecords(std::size_t, std::vector<float>&) { return true; }
+
   Context::Ptr ctx_;
   pclhip_sac_plane_params params_;
+  pclhip_sac_model_params model_;
   pclhip_sac_plane_stats stats_ = pclhip_sac_plane_stats();
   int model_type_ = -1;  // sac_segmentation.h:83-84
   int method_type_ = 0;
   Indices outliers_;
   std::string error_;
+};
+
+// pcl::SACSegmentationFromNormals<PointT, PointNT> (sac_segmentation.h:305-415, impl/sac_segmentation.hpp:374-531) for the
+// plane models: SACMODEL_NORMAL_PLANE and SACMODEL_NORMAL_PARALLEL_PLANE score with the normals (include/pclhip.h), the
+// three of SACSegmentation fall through to it.  Every call needs normals, one per point (:376-386).
+template <typename PointT, typename PointNT>
+class SACSegmentationFromNormals : public SACSegmentation<PointT> {
+ public:
+  using PointCloudNConstPtr = typename PointCloud<PointNT>::ConstPtr;
+  SACSegmentationFromNormals() = default;
+  explicit SACSegmentationFromNormals(Context::Ptr ctx) : SACSegmentation<PointT>(std::move(ctx)) {}
+  void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setNormalDistanceWeight(double w) { this->model_.normal_distance_weight = w; }
+  double getNormalDistanceWeight() const { return this->model_.normal_distance_weight; }
+  // (the class passes no tolerance with it, :452-456: it constrains nothing; pclhip_sac_model_params has eps_dist)
+  void setDistanceFromOrigin(double d) { this->model_.distance_from_origin = d; }
+  double getDistanceFromOrigin() const { return this->model_.distance_from_origin; }
+
+ protected:
+  std::string getClassName() const override { return "SACSegmentationFromNormals"; }
+  bool builds(int model) const override {
+    return SACSegmentation<PointT>::builds(model) || model == SACMODEL_NORMAL_PLANE || model == SACMODEL_NORMAL_PARALLEL_PLANE;
+  }
+  bool normalRecords(std::size_t n, std::vector<float>& out) override {
+    if (!normals_ || normals_->size() != n) {
+      this->error_ = "SACSegmentationFromNormals: setInputNormals with one normal per point first";
+      return false;
+    }
+    out.resize(4 * n);
+    for (std::size_t i = 0; i < n; ++i) {
+      const PointNT& p = (*normals_)[i];
+      out[4 * i] = p.normal_x; out[4 * i + 1] = p.normal_y; out[4 * i + 2] = p.normal_z; out[4 * i + 3] = p.curvature;
+    }
+    return true;
+  }
+
+ private:
+  PointCloudNConstPtr normals_;
 };
 
 }  // namespace pclhip

@@ -3,13 +3,14 @@ VoxelGrid) behind PCL's plugin surface.  Compute lives in libpclhip.so (pcl_amd/
 behind the C ABI of include/pclhip.h; this package is the ctypes host mirror used by tests and
 bench.py.  The C++ mirror of the same surface is include/pclhip/pcl_compat.hpp."""
 from . import synth  # noqa: F401
-from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_PLANE, SYMMETRIC, PclHipError,  # noqa: F401
+from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_NORMAL_PARALLEL_PLANE, SACMODEL_NORMAL_PLANE,  # noqa: F401
+                   SACMODEL_PARALLEL_PLANE, SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PLANE, SYMMETRIC, PclHipError,
                    PclHipUnavailable)
 from .api import (BoundaryEstimation, Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
                   CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, MovingLeastSquares, NormalDistributionsTransform, NormalEstimation,
-                  RadiusOutlierRemoval, SACSegmentation, SampleConsensusPrerejective,
+                  RadiusOutlierRemoval, SACSegmentation, SACSegmentationFromNormals, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

@@ -128,7 +128,21 @@ class SacPlaneTrace(C.Structure):
     _fields_ = [("samples", C.c_int * 3), ("skipped", C.c_int), ("coefficients", C.c_float * 4), ("count", C.c_uint32)]
 
 
+class SacModelParams(C.Structure):
+    _fields_ = [("model_type", C.c_int), ("axis", C.c_float * 3), ("eps_angle", C.c_double),
+                ("normal_distance_weight", C.c_double), ("distance_from_origin", C.c_double), ("eps_dist", C.c_double)]
+
+
+class SacModelTrace(C.Structure):
+    _fields_ = [("samples", C.c_int * 3), ("skipped", C.c_int), ("coefficients", C.c_float * 4), ("count", C.c_uint32),
+                ("valid", C.c_int)]
+
+
 SACMODEL_PLANE = 0   # sample_consensus/model_types.h:47
+SACMODEL_PERPENDICULAR_PLANE = 9
+SACMODEL_NORMAL_PLANE = 11
+SACMODEL_PARALLEL_PLANE = 15
+SACMODEL_NORMAL_PARALLEL_PLANE = 16
 SAC_RANSAC = 0       # sample_consensus/method_types.h:45
 
 NDT_RADIUS, NDT_DIRECT27, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = 0, 1, 2, 3, 4
@@ -246,6 +260,13 @@ SIGNATURES = {
                                            C.POINTER(SacPlaneStats)]),
     "pclhip_sac_plane_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, C.c_double, C.POINTER(C.c_float), C.c_int, _vp]),
     "pclhip_sac_last_trace": (C.c_int, [_vp, C.POINTER(SacPlaneTrace), _u64, C.POINTER(_u64)]),
+    "pclhip_sac_model_params_default": (None, [C.POINTER(SacModelParams)]),
+    "pclhip_sac_segment_model": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.POINTER(SacPlaneParams),
+                                           C.POINTER(SacModelParams), C.POINTER(C.c_float), _vp, _u64, C.POINTER(_u64), _vp,
+                                           _u64, C.POINTER(_u64), C.POINTER(SacPlaneStats)]),
+    "pclhip_sac_model_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.c_double, C.POINTER(SacModelParams),
+                                            C.POINTER(C.c_float), C.c_int, _vp, _vp]),
+    "pclhip_sac_last_model_trace": (C.c_int, [_vp, C.POINTER(SacModelTrace), _u64, C.POINTER(_u64)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

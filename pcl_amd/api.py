@@ -2529,15 +2529,22 @@ class EuclideanClusterExtraction:
 
 class SACSegmentation:
     """pcl::SACSegmentation<PointT> (segmentation/include/pcl/segmentation/sac_segmentation.h:77-330,
-    impl/sac_segmentation.hpp:79-133) for SACMODEL_PLANE under SAC_RANSAC, over pclhip_sac_segment_plane.  The input is an
+    impl/sac_segmentation.hpp:79-133,230-262) for SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE and SACMODEL_PARALLEL_PLANE
+    (setAxis, setEpsAngle) under SAC_RANSAC, over pclhip_sac_segment_plane and pclhip_sac_segment_model.  The input is an
     (n, c >= 3) float32 cloud, numpy or a torch CUDA tensor; the index lists come back in the same kind of array.  The draws
     are a pure function of (seed, trial, slot) (include/pclhip.h): setSeed."""
+
+    _MODELS = (_lib.SACMODEL_PLANE, _lib.SACMODEL_PERPENDICULAR_PLANE, _lib.SACMODEL_PARALLEL_PLANE)
+    _NORMAL_MODELS = (_lib.SACMODEL_NORMAL_PLANE, _lib.SACMODEL_NORMAL_PARALLEL_PLANE)
 
     def __init__(self, ctx=None):
         self.ctx = ctx or default_context()
         self.lib = self.ctx.lib
         self.p = _lib.SacPlaneParams()
         self.lib.pclhip_sac_plane_params_default(C.byref(self.p))
+        self.m = _lib.SacModelParams()
+        self.lib.pclhip_sac_model_params_default(C.byref(self.m))
+        self._normals = None
         self._model = -1       # sac_segmentation.h:83-84: neither is set by default
         self._method = 0
         self._cloud = None
@@ -2549,12 +2556,32 @@ class SACSegmentation:
         return "SACSegmentation"
 
     def setModelType(self, model):
-        if int(model) != _lib.SACMODEL_PLANE:
-            raise NotImplementedError("SACSegmentation: only SACMODEL_PLANE is built")
-        self._model = int(model)
+        model = int(model)
+        if model not in self._MODELS:
+            if model in self._NORMAL_MODELS:  # sac_segmentation.hpp:136-370: SACSegmentation builds no model with normals
+                raise ValueError("%s: model type %d needs SACSegmentationFromNormals" % (self.getClassName(), model))
+            raise NotImplementedError("%s: only the plane models %s are built" % (self.getClassName(), list(self._MODELS)))
+        self._model = model
+        self.m.model_type = model
 
     def getModelType(self):
         return self._model
+
+    def setAxis(self, axis):
+        """The axis of the constrained planes: the normal's for SACMODEL_PERPENDICULAR_PLANE and
+        SACMODEL_NORMAL_PARALLEL_PLANE, one the plane runs along for SACMODEL_PARALLEL_PLANE."""
+        a = np.asarray(axis, np.float32).reshape(3)
+        self.m.axis[0], self.m.axis[1], self.m.axis[2] = float(a[0]), float(a[1]), float(a[2])
+
+    def getAxis(self):
+        return np.array(self.m.axis, np.float32)
+
+    def setEpsAngle(self, eps_angle):
+        """The largest deviation from the axis, in radians (0: no constraint)."""
+        self.m.eps_angle = float(eps_angle)
+
+    def getEpsAngle(self):
+        return float(self.m.eps_angle)
 
     def setMethodType(self, method):
         if int(method) != _lib.SAC_RANSAC:
@@ -2613,7 +2640,7 @@ class SACSegmentation:
 
     def _inputs(self):
         assert self._cloud is not None, "setInputCloud first"
-        if self._model != _lib.SACMODEL_PLANE:
+        if self._model < 0:
             raise ValueError("SACSegmentation: no model type was set (setModelType(SACMODEL_PLANE))")
         ptr, stride, n, keep = _cloud(self._cloud)
         idx, ip, ni = None, None, 0
@@ -2629,6 +2656,20 @@ class SACSegmentation:
                 idx = np.zeros(1, np.int32)
                 ip = C.c_void_p(idx.ctypes.data)
         return ptr, stride, n, ip, ni, (keep, idx)
+
+    def _through_model(self):
+        """the call goes through pclhip_sac_segment_model / _evaluate (the plain plane keeps the plane's entry points)"""
+        return self._model != _lib.SACMODEL_PLANE
+
+    def _normal_records(self, n):
+        """-> (pointer, stride_bytes, keepalive) of the (n, >= 4) normal records; (None, 0, None) without normals"""
+        if self._normals is None:
+            return None, 0, None
+        nptr, nstride, nn, nkeep = _cloud_rows(self._normals)
+        if nn != n or nstride < 16:
+            raise ValueError("%s: the normals must be (n, >= 4) records (nx, ny, nz, curvature), one per record of the cloud"
+                             % self.getClassName())
+        return nptr, nstride, nkeep
 
     def segment(self, inliers_capacity=None, outliers_capacity=None):
         """segment(PointIndices&, ModelCoefficients&) -> (inliers int32, coefficients float32 [4]); both empty when no model
@@ -2651,8 +2692,14 @@ class SACSegmentation:
         st = _lib.SacPlaneStats()
         self._outliers = None
         self._stats = None
-        rc = self.lib.pclhip_sac_segment_plane(self.ctx.h, ptr, n, stride, ip, ni, C.byref(self.p), _fp(coeff), pin, cap_in,
-                                               C.byref(n_in), pout, cap_out, C.byref(n_out), C.byref(st))
+        if self._through_model():
+            nptr, nstride, nkeep = self._normal_records(n)
+            rc = self.lib.pclhip_sac_segment_model(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni, C.byref(self.p),
+                                                   C.byref(self.m), _fp(coeff), pin, cap_in, C.byref(n_in), pout, cap_out,
+                                                   C.byref(n_out), C.byref(st))
+        else:
+            rc = self.lib.pclhip_sac_segment_plane(self.ctx.h, ptr, n, stride, ip, ni, C.byref(self.p), _fp(coeff), pin, cap_in,
+                                                   C.byref(n_in), pout, cap_out, C.byref(n_out), C.byref(st))
         self._stats = dict(trials=int(st.trials), iterations=int(st.iterations), skipped=int(st.skipped),
                            batches=int(st.batches), best_trial=int(st.best_trial), best_count=int(st.best_count),
                            refined=bool(st.refined), count_ms=float(st.count_ms), total_ms=float(st.total_ms),
@@ -2674,24 +2721,80 @@ class SACSegmentation:
         return self._stats
 
     def trace(self, capacity=65536):
-        """One dict per trial the last segment() consumed: samples, skipped, coefficients, count."""
+        """One dict per trial the last segment() consumed: samples, skipped, coefficients, count, valid (False for a
+        skipped trial and for a hypothesis that failed its model's gate: isModelValid)."""
         n = C.c_uint64(0)
-        check(self.lib.pclhip_sac_last_trace(self.ctx.h, None, 0, C.byref(n)), self.ctx.h)
+        check(self.lib.pclhip_sac_last_model_trace(self.ctx.h, None, 0, C.byref(n)), self.ctx.h)
         m = min(int(n.value), int(capacity))
-        buf = (_lib.SacPlaneTrace * max(1, m))()
-        check(self.lib.pclhip_sac_last_trace(self.ctx.h, buf, m, C.byref(n)), self.ctx.h)
+        buf = (_lib.SacModelTrace * max(1, m))()
+        check(self.lib.pclhip_sac_last_model_trace(self.ctx.h, buf, m, C.byref(n)), self.ctx.h)
         return [dict(samples=list(t.samples), skipped=bool(t.skipped), coefficients=np.array(t.coefficients, np.float32),
-                     count=int(t.count)) for t in buf[:m]]
+                     count=int(t.count), valid=bool(t.valid)) for t in buf[:m]]
 
-    def countWithinDistance(self, models):
-        """SampleConsensusModelPlane::countWithinDistance of (H, 4) coefficient rows over the point set, batched ->
-        (H,) uint32."""
+    def evaluate(self, models):
+        """countWithinDistance and isModelValid of (H, 4) coefficient rows -> ((H,) uint32 counts, (H,) bool valid)."""
         ptr, stride, n, ip, ni, keep = self._inputs()
         M = np.ascontiguousarray(models, np.float32).reshape(-1, 4)
         cnt = np.zeros(len(M), np.uint32)
-        check(self.lib.pclhip_sac_plane_evaluate(self.ctx.h, ptr, n, stride, ip, ni, float(self.p.distance_threshold), _fp(M),
-                                                 len(M), C.c_void_p(cnt.ctypes.data)), self.ctx.h)
-        return cnt
+        valid = np.ones(len(M), np.uint8)
+        if self._through_model():
+            nptr, nstride, nkeep = self._normal_records(n)
+            check(self.lib.pclhip_sac_model_evaluate(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni,
+                                                     float(self.p.distance_threshold), C.byref(self.m), _fp(M), len(M),
+                                                     C.c_void_p(cnt.ctypes.data), C.c_void_p(valid.ctypes.data)), self.ctx.h)
+        else:
+            check(self.lib.pclhip_sac_plane_evaluate(self.ctx.h, ptr, n, stride, ip, ni, float(self.p.distance_threshold), _fp(M),
+                                                     len(M), C.c_void_p(cnt.ctypes.data)), self.ctx.h)
+        return cnt, valid.astype(bool)
+
+    def countWithinDistance(self, models):
+        """SampleConsensusModel::countWithinDistance of (H, 4) coefficient rows over the point set, batched ->
+        (H,) uint32 (0 for a hypothesis that fails its model's gate)."""
+        return self.evaluate(models)[0]
+
+
+class SACSegmentationFromNormals(SACSegmentation):
+    """pcl::SACSegmentationFromNormals<PointT, PointNT> (segmentation/include/pcl/segmentation/sac_segmentation.h:305-415,
+    impl/sac_segmentation.hpp:374-531) for the plane models: SACMODEL_NORMAL_PLANE and SACMODEL_NORMAL_PARALLEL_PLANE score
+    with the points' normals (include/pclhip.h), the three models of SACSegmentation are built as there.  The normals are
+    (n, >= 4) float32 records (nx, ny, nz, curvature), one per record of the cloud (what NormalEstimation.compute() returns),
+    numpy or a torch CUDA tensor; every call needs them, as the reference's does.  Every model goes through
+    pclhip_sac_segment_model."""
+
+    _MODELS = SACSegmentation._MODELS + SACSegmentation._NORMAL_MODELS
+    _NORMAL_MODELS = ()
+
+    def getClassName(self):
+        return "SACSegmentationFromNormals"
+
+    def setInputNormals(self, normals):
+        self._normals = normals
+
+    def getInputNormals(self):
+        return self._normals
+
+    def setNormalDistanceWeight(self, weight):
+        """The share of the angle between a point's normal and the plane's in the distance (default 0.1)."""
+        self.m.normal_distance_weight = float(weight)
+
+    def getNormalDistanceWeight(self):
+        return float(self.m.normal_distance_weight)
+
+    def setDistanceFromOrigin(self, d):
+        """SACMODEL_NORMAL_PARALLEL_PLANE's distance from the origin.  The class sets no tolerance for it
+        (sac_segmentation.hpp:440-468), so it constrains nothing; the C interface has eps_dist."""
+        self.m.distance_from_origin = float(d)
+
+    def getDistanceFromOrigin(self):
+        return float(self.m.distance_from_origin)
+
+    def _through_model(self):
+        return True
+
+    def _normal_records(self, n):
+        if self._normals is None:  # sac_segmentation.hpp:376-380
+            raise ValueError("SACSegmentationFromNormals: setInputNormals first")
+        return super()._normal_records(n)
 
 
 def featureKSearch(ctx, target_rows, query_rows, k):

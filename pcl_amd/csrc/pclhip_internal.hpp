@@ -266,6 +266,7 @@ struct pclhip_ctx {
   bool arena_tried = false;             // the automatic reservation was attempted (once per context)
   // the trials the last pclhip_sac_segment_plane consumed (sac.hpp; pclhip_sac_last_trace)
   std::vector<pclhip_sac_plane_trace> sac_trace;
+  std::vector<uint8_t> sac_trace_valid;  // the gate's bit of each (sac_models.hpp; pclhip_sac_last_model_trace)
 };
 
 struct pclhip_index {

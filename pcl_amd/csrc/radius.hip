@@ -448,6 +448,8 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 
 // SACSegmentation (planes): batched RANSAC scoring, one pass over the points per batch of hypotheses
 #include "sac.hpp"
+// ... its constrained planes (a gate per hypothesis) and SACSegmentationFromNormals' plane (the distance with the normals)
+#include "sac_models.hpp"
 
 // SampleConsensusPrerejective: its scoring pass is a bounded 1-NN traversal of the target index
 #include "scp.hpp"

@@ -20,6 +20,7 @@
 // list in block_sums.hpp's fixed order), block_sums_finalize_kernel, sac_refit_kernel (one thread: covariance in double
 // rounded once to float, normals_math.hpp's eigen33 path), then flags, scan and compaction again; the complement list from
 // the same flags.  ONE more read-back: the coefficients and the list lengths.
+// The host side of the call is sac_segment_run in sac_models.hpp, shared with the constrained and the normal plane models.
 #pragma once
 
 #include <cfloat>
@@ -50,7 +51,8 @@ struct SacDev {         // device-resident results of a call
   uint32_t tot[4];      // scan totals of the flags: tot[0] = inliers
   uint32_t bad_index;   // an entry of `indices` outside the cloud
   uint32_t refined;
-  uint32_t pad[2];
+  uint32_t invalid;     // the coefficients fail their model's gate (sac_models.hpp): the selection is empty
+  uint32_t pad;
 };
 
 inline dim3 sac_blocks_of(uint64_t n) { return dim3(uint32_t((n + SAC_BLOCK - 1) / SAC_BLOCK)); }
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(SAC_BLOCK) void sac_flag_kernel(const float4* __res
   const float a = st->coef[0], b = st->coef[1], c = st->coef[2], d = st->coef[3];
   const float4 p = pts[i];
   const float e = __fadd_rn(__fadd_rn(__fmul_rn(a, p.x), __fmul_rn(b, p.y)), __fadd_rn(__fmul_rn(c, p.z), d));
-  flag[i] = __builtin_fabsf(e) < thr ? 1u : 0u;
+  flag[i] = st->invalid == 0u && __builtin_fabsf(e) < thr ? 1u : 0u;
 }
 
 // the two lists from one set of flags, in the order of the point set: cloud indices of the inliers and of the rest
@@ -295,6 +297,13 @@ pclhip_status sac_copy_out(pclhip_ctx* ctx, int32_t* out, const int32_t* dev, ui
   return PCLHIP_OK;
 }
 
+// the call, for the plane and for the models of sac_models.hpp (defined there: radius.hip includes it after this file)
+pclhip_status sac_segment_run(pclhip_ctx* ctx, const char* fn, const void* cloud, uint64_t n_rec, size_t stride,
+                              const void* normals, size_t nstride, const int32_t* indices, uint64_t n_indices,
+                              const pclhip_sac_plane_params* P, const pclhip_sac_model_params* MP, float out_coeff[4],
+                              int32_t* out_inliers, uint64_t inliers_capacity, uint64_t* out_n_inliers, int32_t* out_outliers,
+                              uint64_t outliers_capacity, uint64_t* out_n_outliers, pclhip_sac_plane_stats* out_stats);
+
 }  // namespace
 }  // namespace pclhip
 
@@ -356,193 +365,9 @@ pclhip_status pclhip_sac_segment_plane(pclhip_ctx* ctx, const void* cloud, uint6
                                        float out_coeff[4], int32_t* out_inliers, uint64_t inliers_capacity,
                                        uint64_t* out_n_inliers, int32_t* out_outliers, uint64_t outliers_capacity,
                                        uint64_t* out_n_outliers, pclhip_sac_plane_stats* out_stats) {
-  using namespace pclhip;
-  if (!ctx || !P || !out_coeff || !out_n_inliers) return PCLHIP_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
-  *out_n_inliers = 0;
-  if (out_n_outliers) *out_n_outliers = 0;
-  for (int i = 0; i < 4; ++i) out_coeff[i] = 0.0f;
-  pclhip_sac_plane_stats stats;
-  std::memset(&stats, 0, sizeof stats);
-  stats.best_trial = -1;
-  if (out_stats) *out_stats = stats;
-  ctx->sac_trace.clear();
-  pclhip_status rc = sac_checked_params(ctx, cloud, n_rec, stride, indices, n_indices);
-  if (rc != PCLHIP_OK) return rc;
-  PCLHIP_REQUIRE(ctx, P->max_iterations >= 0 && P->max_iterations <= 100000000, "max_iterations must be in 0 .. 1e8");
-  PCLHIP_REQUIRE(ctx, P->probability >= 0.0 && P->probability <= 1.0, "the probability must be in [0, 1]");
-  PCLHIP_REQUIRE(ctx, P->batch_size >= 0 && P->batch_size <= SAC_MAX_BATCH, "batch_size must be in 0 .. 1024");
-  PCLHIP_REQUIRE(ctx, (out_inliers != nullptr || inliers_capacity == 0) && (out_outliers != nullptr || outliers_capacity == 0),
-                 "a capacity without a buffer");
-  PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DeviceScope scope(ctx);
-  hipEvent_t ev_call[2] = {nullptr, nullptr};
-  PCLHIP_CHECK_HIP(ctx, scope.event(&ev_call[0]));
-  PCLHIP_CHECK_HIP(ctx, scope.event(&ev_call[1]));
-  (void)hipEventRecord(ev_call[0], s);
-  SacDev* st = nullptr;
-  PCLHIP_CHECK_HIP(ctx, scope.alloc(&st, sizeof(SacDev)));
-  PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(st, 0, sizeof(SacDev), s));
-  SacCloud pc;
-  if ((rc = sac_stage(ctx, scope, cloud, n_rec, stride, indices, n_indices, st, &pc)) != PCLHIP_OK) return rc;
-  const uint32_t n = pc.n;
-  const float thr = float(P->distance_threshold);
-
-  // ---- the trials ----
-  sac::Replay rp;
-  rp.start(P->max_iterations, P->probability, n > 0 ? n : 1);
-  pclhip_sac_plane_trace best_rec;
-  std::memset(&best_rec, 0, sizeof best_rec);
-  std::vector<hipEvent_t> ev_count;
-  if (n >= 3) {  // (fewer points: getSamples finds no sample, ransac.hpp:120-124)
-    const int cap = P->batch_size > 0 ? P->batch_size : SAC_MAX_BATCH;
-    pclhip_sac_plane_trace* rec = nullptr;
-    float4* models = nullptr;
-    uint32_t* counts = nullptr;
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&rec, size_t(cap) * sizeof(pclhip_sac_plane_trace)));
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&models, size_t(cap) * sizeof(float4)));
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&counts, size_t(cap) * 4));
-    std::vector<pclhip_sac_plane_trace> hrec(static_cast<size_t>(cap));
-    std::vector<uint32_t> hcnt(static_cast<size_t>(cap));
-    const uint32_t grid = sac_count_grid(ctx, n);
-    uint64_t t0 = 0;
-    int B = P->batch_size > 0 ? P->batch_size : SAC_AUTO_BATCH;
-    bool first = true;
-    while (!rp.done) {
-      // no batch holds more trials than the loop can still score: one pass covers a call that meets no skip
-      const int64_t left = int64_t(P->max_iterations) + 1 - rp.iterations;
-      const uint32_t nit = uint32_t(left < B ? (left > 0 ? left : 1) : B);
-      hipEvent_t ea = nullptr, eb = nullptr;
-      PCLHIP_CHECK_HIP(ctx, scope.event(&ea));
-      PCLHIP_CHECK_HIP(ctx, scope.event(&eb));
-      hipLaunchKernelGGL(sac_hypothesis_kernel, sac_blocks_of(nit), dim3(SAC_BLOCK), 0, s, P->seed, uint32_t(t0), nit, n, pc.pts,
-                         rec, models);
-      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(counts, 0, size_t(nit) * 4, s));
-      (void)hipEventRecord(ea, s);
-      hipLaunchKernelGGL(sac_count_kernel, dim3(grid), dim3(SAC_BLOCK), 0, s, pc.pts, n, models, nit, thr, counts);
-      (void)hipEventRecord(eb, s);
-      PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-      ev_count.push_back(ea);
-      ev_count.push_back(eb);
-      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(hrec.data(), rec, size_t(nit) * sizeof(pclhip_sac_plane_trace), hipMemcpyDeviceToHost, s));
-      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(hcnt.data(), counts, size_t(nit) * 4, hipMemcpyDeviceToHost, s));
-      SacDev hst;
-      if (first) PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&hst, st, sizeof hst, hipMemcpyDeviceToHost, s));
-      PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
-      if (first) PCLHIP_REQUIRE(ctx, hst.bad_index == 0u, "an entry of indices lies outside the cloud");
-      first = false;
-      ++stats.batches;
-      for (uint32_t t = 0; t < nit; ++t) {
-        hrec[t].count = hrec[t].skipped ? 0u : hcnt[t];
-        const uint32_t before = rp.best;
-        const bool more = rp.feed(hrec[t].skipped != 0, hrec[t].count);
-        if (rp.best != before) best_rec = hrec[t];
-        if (ctx->sac_trace.size() < SAC_TRACE_MAX) ctx->sac_trace.push_back(hrec[t]);
-        if (!more) break;
-      }
-      t0 += nit;
-      if (P->batch_size == 0 && B < SAC_MAX_BATCH) B *= 2;
-      if (t0 + uint64_t(SAC_MAX_BATCH) >= 0xFFFFFFFFull) break;  // (the draw counter holds 32 bits)
-    }
-  } else if (n > 0) {
-    SacDev hst;
-    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&hst, st, sizeof hst, hipMemcpyDeviceToHost, s));
-    PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
-    PCLHIP_REQUIRE(ctx, hst.bad_index == 0u, "an entry of indices lies outside the cloud");
-  }
-  stats.trials = rp.trials;
-  stats.iterations = rp.iterations;
-  stats.skipped = rp.skipped;
-  stats.best_trial = int(rp.best_trial);
-  stats.best_count = rp.best;
-
-  // ---- the lists ----
-  const bool found = rp.best_trial >= 0;
-  uint64_t n_in = 0;
-  SacDev hst;
-  std::memset(&hst, 0, sizeof hst);
-  int32_t *inl = nullptr, *outl = nullptr;
-  if (found) {
-    uint32_t *flag = nullptr, *excl = nullptr, *pos = nullptr;
-    uint2* part = nullptr;
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&flag, size_t(n) * 4));
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&excl, size_t(n) * 4));
-    PCLHIP_CHECK_HIP(ctx, scope.alloc(&part, size_t((uint64_t(n) + SC_BLOCK - 1) / SC_BLOCK + 1) * sizeof(uint2)));
-    const bool inl_dev = out_inliers && is_device_pointer(out_inliers) && inliers_capacity >= n;
-    const bool outl_dev = out_outliers && is_device_pointer(out_outliers) && outliers_capacity >= n;
-    if (inl_dev) inl = out_inliers; else PCLHIP_CHECK_HIP(ctx, scope.alloc(&inl, size_t(n) * 4));
-    if (out_outliers || out_n_outliers) {
-      if (outl_dev) outl = out_outliers; else PCLHIP_CHECK_HIP(ctx, scope.alloc(&outl, size_t(n) * 4));
-    }
-    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(st->coef, best_rec.coefficients, 16, hipMemcpyHostToDevice, s));
-    auto select = [&]() {
-      (void)hipMemsetAsync(st->tot, 0, 16, s);
-      hipLaunchKernelGGL(sac_flag_kernel, sac_blocks_of(n), dim3(SAC_BLOCK), 0, s, pc.pts, n, st, thr, flag);
-      launch_scan_u32(s, flag, n, part, st->tot, excl);
-    };
-    select();
-    if (P->optimize_coefficients && rp.best > 3u) {
-      // the first selection has rp.best inliers by construction: the same expression on the same points
-      const uint32_t m = rp.best;
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&pos, size_t(m) * 4));
-      uint32_t mblocks = (m + SAC_BLOCK - 1) / SAC_BLOCK;
-      if (mblocks > uint32_t(SAC_MOMENT_BLOCKS)) mblocks = uint32_t(SAC_MOMENT_BLOCKS);
-      double *partials = nullptr, *sums = nullptr;
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&partials, size_t(mblocks) * 9 * sizeof(double)));
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&sums, 9 * sizeof(double)));
-      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(pos, 0, size_t(m) * 4, s));
-      hipLaunchKernelGGL(sac_positions_kernel, sac_blocks_of(n), dim3(SAC_BLOCK), 0, s, flag, excl, n, pos, m);
-      hipLaunchKernelGGL(sac_moments_kernel, dim3(mblocks), dim3(SAC_BLOCK), 0, s, pc.pts, pos, m, partials);
-      hipLaunchKernelGGL(block_sums_finalize_kernel<9>, dim3(9), dim3(WAVE), 0, s, partials, int(mblocks), sums);
-      hipLaunchKernelGGL(sac_refit_kernel, dim3(1), dim3(WAVE), 0, s, sums, pc.pts, pos, m, st);
-      select();
-    }
-    hipLaunchKernelGGL(sac_lists_kernel, sac_blocks_of(n), dim3(SAC_BLOCK), 0, s, flag, excl, n, pc.idx, inl, outl);
-    PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&hst, st, sizeof hst, hipMemcpyDeviceToHost, s));
-    PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
-    n_in = hst.tot[0];
-    for (int i = 0; i < 4; ++i) out_coeff[i] = hst.coef[i];
-    stats.refined = int(hst.refined);
-  }
-  const uint64_t n_out = uint64_t(n) - n_in;
-  *out_n_inliers = n_in;
-  if (out_n_outliers) *out_n_outliers = n_out;
-  const bool short_in = out_inliers != nullptr && inliers_capacity < n_in;
-  const bool short_out = out_outliers != nullptr && outliers_capacity < n_out;
-  if (!short_in && !short_out) {
-    if (found) {
-      if ((rc = sac_copy_out(ctx, out_inliers, inl, n_in)) != PCLHIP_OK) return rc;
-      if ((rc = sac_copy_out(ctx, out_outliers, outl, n_out)) != PCLHIP_OK) return rc;
-    } else if (out_outliers != nullptr && n > 0) {  // no model: everything is left over
-      uint32_t *flag = nullptr, *excl = nullptr;
-      int32_t* all = nullptr;
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&flag, size_t(n) * 4));
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&excl, size_t(n) * 4));
-      PCLHIP_CHECK_HIP(ctx, scope.alloc(&all, size_t(n) * 4));
-      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(flag, 0, size_t(n) * 4, s));
-      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(excl, 0, size_t(n) * 4, s));
-      hipLaunchKernelGGL(sac_lists_kernel, sac_blocks_of(n), dim3(SAC_BLOCK), 0, s, flag, excl, n, pc.idx,
-                         static_cast<int32_t*>(nullptr), all);
-      PCLHIP_CHECK_HIP(ctx, hipGetLastError());
-      if ((rc = sac_copy_out(ctx, out_outliers, all, n_out)) != PCLHIP_OK) return rc;
-    }
-  }
-  (void)hipEventRecord(ev_call[1], s);
-  PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
-  for (size_t p = 0; p + 1 < ev_count.size(); p += 2) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev_count[p], ev_count[p + 1]) == hipSuccess) stats.count_ms += ms;
-  }
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, ev_call[0], ev_call[1]) == hipSuccess) stats.total_ms = ms;
-  if (out_stats) *out_stats = stats;
-  if (short_in || short_out) {
-    set_error(ctx, "pclhip_sac_segment_plane: capacity too small (the counts hold the required sizes)");
-    return PCLHIP_ERR_OVERFLOW;
-  }
-  return PCLHIP_OK;
+  return pclhip::sac_segment_run(ctx, "pclhip_sac_segment_plane", cloud, n_rec, stride, nullptr, 0, indices, n_indices, P, nullptr,
+                                 out_coeff, out_inliers, inliers_capacity, out_n_inliers, out_outliers, outliers_capacity,
+                                 out_n_outliers, out_stats);
 }
 
 pclhip_status pclhip_sac_last_trace(pclhip_ctx* ctx, pclhip_sac_plane_trace* buf, uint64_t capacity, uint64_t* count) {
