@@ -434,6 +434,48 @@ PCLHIP_API pclhip_status pclhip_euclidean_clusters(pclhip_index* index, double t
  * of unions its hook kernel attempted (a hit under another root; depends on the order the device worked in). */
 PCLHIP_API void pclhip_index_last_cluster_stats(const pclhip_index* index, double* hook_ms, double* flatten_ms,
                                                 uint64_t* unions);
+/* pcl::RegionGrowing<PointT, NormalT>::extract (segmentation/.../impl/region_growing.hpp:231-548) in smooth mode: the
+ * segmentation of the index's points into smooth regions from normals and curvatures.  The reference floods breadth-first
+ * from seeds in curvature order; the kernels (pcl_amd/csrc/region_growing.hpp) compute the same labels from an order-free
+ * restatement, so two calls give the same bytes.  The index defines the set of points, as for pclhip_euclidean_clusters.
+ * Segments are numbered in the order their seeds are taken (ascending curvature); those outside [min_cluster_size,
+ * max_cluster_size] are dropped and the rest keeps that order; every segment's indices ascend.
+ * Deviations: curvature ties are broken by the lower original index (the reference's std::sort leaves them open; -0 ties
+ * with +0); k-NN ties go to the lower index; a non-finite point is in no segment, label -1 (the reference makes it a
+ * segment of one); a NaN normal passes the smoothness test as in the reference (NaN < c is false).
+ * Refused (PCLHIP_ERR_INVALID, with a message): residual_test != 0 (whether a point expands would depend on who reached
+ * it first, i.e. on the flood's order inside a region); smooth_mode == 0; number_of_neighbours > 64 (an edge mask is one
+ * 64-bit word) or < 0; a NaN curvature of an indexed point (the reference's sort has no defined order there); a NaN
+ * smoothness threshold.  An index built with rescale values, or with indices that name a record twice, is
+ * PCLHIP_ERR_STATE.  number_of_neighbours == 0 and an empty
+ * index give zero segments (:303-304).  curvature_test == 0 (every point expands) is reachable from this interface only:
+ * the reference's setter switches the residual test on with it.
+ * Not built: RegionGrowingRGB, a search surface other than the input, a pcl_plugin.hpp class, multi-GPU. */
+typedef struct {
+  int number_of_neighbours;     /* 30 */
+  float smoothness_threshold;   /* 30.0f / 180.0f * float(M_PI) */
+  float curvature_threshold;    /* 0.05f */
+  int curvature_test;           /* 1 */
+  int smooth_mode;              /* 1 */
+  int residual_test;            /* 0 */
+  float residual_threshold;     /* 0.05f, stored only */
+  uint32_t min_cluster_size;    /* 1 */
+  uint32_t max_cluster_size;    /* UINT32_MAX */
+} pclhip_region_growing_params;
+PCLHIP_API void pclhip_region_growing_params_default(pclhip_region_growing_params* params);
+/*   normals      (host or device) one byte-strided (nx, ny, nz, curvature) float record per ORIGINAL point
+ *   out_labels, out_offsets, out_indices, the capacities and the counts: as for pclhip_euclidean_clusters -- the counts are
+ *   always written, PCLHIP_ERR_OVERFLOW comes after the counts and the labels. */
+PCLHIP_API pclhip_status pclhip_region_growing(pclhip_index* index, const void* normals, size_t normals_stride,
+                                               const pclhip_region_growing_params* params, int32_t* out_labels,
+                                               uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices,
+                                               uint64_t indices_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+/* Of the last pclhip_region_growing on this index: the GPU time (ms) of the k-NN lists, of the collapse and of the two
+ * round loops; the rounds of phase 1 (propagation) and of phase 2 (leftover points); the unions the collapse attempted
+ * (depends on the order the device worked in); the number of leftover points.  Every pointer is optional. */
+PCLHIP_API void pclhip_index_last_region_growing_stats(const pclhip_index* index, double* lists_ms, double* collapse_ms,
+                                                       double* phase1_ms, double* phase2_ms, uint32_t* phase1_rounds,
+                                                       uint32_t* phase2_rounds, uint64_t* unions, uint64_t* leftover);
 /* GPU time (ms) of the last pclhip_knn / pclhip_normals traversal kernel on this index. */
 PCLHIP_API double pclhip_index_last_kernel_ms(const pclhip_index* index);
 /* Supply target normals computed elsewhere (e.g. a pcl::PointNormal target: normals = points + 16,

@@ -2127,6 +2127,114 @@ class EuclideanClusterExtraction : public PCLBase<PointT> {
   std::string error_;
 };
 
+// pcl::RegionGrowing<PointT, NormalT> (segmentation/include/pcl/segmentation/region_growing.h:66-340,
+// impl/region_growing.hpp:231-548) over pclhip_region_growing: smooth mode with the curvature test and without the residual
+// test (the reference's defaults).  The segments come in the order their seeds were taken, indices ascending.  What is
+// not built leaves the output empty and says why in getLastError(): the residual test, setCurvatureTestFlag(false) (the
+// reference switches the residual test on with it, :120-126), setSmoothModeFlag(false), more than 64 neighbours, a NaN
+// curvature.  NormalT needs normal_x/y/z and curvature (Normal, PointNormal).
+template <typename PointT, typename NormalT>
+class RegionGrowing : public PCLBase<PointT> {
+ public:
+  using KdTree = search::Search<PointT>;
+  using KdTreePtr = typename KdTree::Ptr;
+  using Normal = PointCloud<NormalT>;
+  using NormalPtr = typename Normal::ConstPtr;
+  RegionGrowing() : RegionGrowing(Context::defaultContext()) {}
+  explicit RegionGrowing(Context::Ptr ctx) : ctx_(std::move(ctx)) { pclhip_region_growing_params_default(&prm_); }
+  uindex_t getMinClusterSize() const { return prm_.min_cluster_size; }
+  void setMinClusterSize(uindex_t n) { prm_.min_cluster_size = n; }
+  uindex_t getMaxClusterSize() const { return prm_.max_cluster_size; }
+  void setMaxClusterSize(uindex_t n) { prm_.max_cluster_size = n; }
+  bool getSmoothModeFlag() const { return prm_.smooth_mode != 0; }
+  void setSmoothModeFlag(bool value) { prm_.smooth_mode = value ? 1 : 0; }
+  bool getCurvatureTestFlag() const { return prm_.curvature_test != 0; }
+  void setCurvatureTestFlag(bool value) {  // :120-126
+    prm_.curvature_test = value ? 1 : 0;
+    if (!value && prm_.residual_test == 0) prm_.residual_test = 1;
+  }
+  bool getResidualTestFlag() const { return prm_.residual_test != 0; }
+  void setResidualTestFlag(bool value) {  // :137-143
+    prm_.residual_test = value ? 1 : 0;
+    if (!value && prm_.curvature_test == 0) prm_.curvature_test = 1;
+  }
+  float getSmoothnessThreshold() const { return prm_.smoothness_threshold; }
+  void setSmoothnessThreshold(float theta) { prm_.smoothness_threshold = theta; }
+  float getResidualThreshold() const { return prm_.residual_threshold; }
+  void setResidualThreshold(float residual) { prm_.residual_threshold = residual; }
+  float getCurvatureThreshold() const { return prm_.curvature_threshold; }
+  void setCurvatureThreshold(float curvature) { prm_.curvature_threshold = curvature; }
+  unsigned int getNumberOfNeighbours() const { return unsigned(prm_.number_of_neighbours); }
+  void setNumberOfNeighbours(unsigned int k) { prm_.number_of_neighbours = int(k > 0x7FFFFFFFu ? 0x7FFFFFFFu : k); }
+  // a pclhip::search::KdTree is rebuilt over (input, indices) and used; any other Search is ignored
+  void setSearchMethod(const KdTreePtr& tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setInputNormals(const NormalPtr& normals) { normals_ = normals; }
+  NormalPtr getInputNormals() const { return normals_; }
+  const std::string& getLastError() const { return error_; }
+  // per record of the input: the number of its segment in the last extract(), -1 for a record in no returned segment
+  const std::vector<std::int32_t>& getLabels() const { return labels_; }
+
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    clusters_.clear();
+    labels_.clear();
+    error_.clear();
+    // prepareForSegmentation (:278-304): no cloud, no normals, normals of another size, no neighbours -> no segment
+    if (!this->input_ || this->input_->empty() || !ctx_ || !ctx_->ok()) return;
+    if (!normals_ || normals_->size() != this->input_->size() || prm_.number_of_neighbours == 0) return;
+    const bool subset = this->indices_ && !this->fake_indices_;
+    if (subset && this->indices_->empty()) return;
+    auto tree = std::dynamic_pointer_cast<search::KdTree<PointT>>(tree_);
+    if (!tree) tree = std::make_shared<search::KdTree<PointT>>(ctx_);
+    if (!tree->setInputCloud(this->input_, subset ? IndicesConstPtr(this->indices_) : IndicesConstPtr())) {
+      error_ = pclhip_last_error(ctx_->get());
+      return;
+    }
+    const std::size_t n = this->input_->size();
+    std::vector<float> rec(4 * n);
+    for (std::size_t i = 0; i < n; ++i) {
+      const NormalT& p = (*normals_)[i];
+      rec[4 * i] = p.normal_x; rec[4 * i + 1] = p.normal_y; rec[4 * i + 2] = p.normal_z; rec[4 * i + 3] = p.curvature;
+    }
+    std::vector<std::uint64_t> offsets(n + 1, 0);
+    Indices flat(n);
+    labels_.assign(n, -1);
+    std::uint64_t k = 0, nc = 0;
+    if (pclhip_region_growing(tree->handle(), rec.data(), 16, &prm_, labels_.data(), offsets.data(), n + 1, flat.data(), n, &k,
+                              &nc) != PCLHIP_OK) {
+      error_ = pclhip_last_error(tree->context()->get());
+      labels_.clear();
+      return;
+    }
+    clusters_.resize(std::size_t(k));
+    for (std::size_t c = 0; c < std::size_t(k); ++c)
+      clusters_[c].indices.assign(flat.begin() + long(offsets[c]), flat.begin() + long(offsets[c + 1]));
+    clusters = clusters_;
+  }
+
+  // the segment of the last extract() that holds record `index` (the segmentation is run if it has not been); empty when
+  // the record is in no returned segment
+  void getSegmentFromPoint(index_t index, PointIndices& cluster) {
+    cluster.indices.clear();
+    if (labels_.empty() && error_.empty()) {
+      std::vector<PointIndices> all;
+      extract(all);
+    }
+    if (index < 0 || std::size_t(index) >= labels_.size() || labels_[std::size_t(index)] < 0) return;
+    cluster = clusters_[std::size_t(labels_[std::size_t(index)])];
+  }
+
+ private:
+  Context::Ptr ctx_;
+  KdTreePtr tree_;
+  NormalPtr normals_;
+  pclhip_region_growing_params prm_;
+  std::vector<PointIndices> clusters_;
+  std::vector<std::int32_t> labels_;
+  std::string error_;
+};
+
 // pcl::Keypoint<PointInT, PointOutT> (keypoints/include/pcl/keypoints/keypoint.h:52-209): compute() checks the input, calls
 // the detector's detectKeypoints() and leaves the keypoints' indices behind for getKeypointsIndices().
 template <typename PointInT, typename PointOutT>

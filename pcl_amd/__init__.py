@@ -11,6 +11,6 @@ from .api import (BoundaryEstimation, Communicator, Context, CorrespondenceEstim
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, MovingLeastSquares, NormalDistributionsTransform, NormalEstimation,
-                  RadiusOutlierRemoval, SACSegmentation, SACSegmentationFromNormals, SampleConsensusPrerejective,
+                  RadiusOutlierRemoval, RegionGrowing, SACSegmentation, SACSegmentationFromNormals, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

@@ -161,6 +161,12 @@ class SorStats(C.Structure):
                 ("sq_sum", C.c_double), ("valid", C.c_uint64)]
 
 
+class RegionGrowingParams(C.Structure):
+    _fields_ = [("number_of_neighbours", C.c_int), ("smoothness_threshold", C.c_float), ("curvature_threshold", C.c_float),
+                ("curvature_test", C.c_int), ("smooth_mode", C.c_int), ("residual_test", C.c_int),
+                ("residual_threshold", C.c_float), ("min_cluster_size", C.c_uint32), ("max_cluster_size", C.c_uint32)]
+
+
 COMM_ID_BYTES = 128
 
 
@@ -303,6 +309,12 @@ SIGNATURES = {
     "pclhip_euclidean_clusters": (C.c_int, [_vp, C.c_double, C.c_uint32, C.c_uint32, _vp, C.POINTER(_u64), _u64, _vp, _u64,
                                             C.POINTER(_u64), C.POINTER(_u64)]),
     "pclhip_index_last_cluster_stats": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_u64)]),
+    "pclhip_region_growing_params_default": (None, [C.POINTER(RegionGrowingParams)]),
+    "pclhip_region_growing": (C.c_int, [_vp, _vp, _sz, C.POINTER(RegionGrowingParams), _vp, C.POINTER(_u64), _u64, _vp, _u64,
+                                        C.POINTER(_u64), C.POINTER(_u64)]),
+    "pclhip_index_last_region_growing_stats": (None, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                      C.POINTER(_u64), C.POINTER(_u64)]),
     "pclhip_solve_transformation": (C.c_int, [C.POINTER(C.c_double), C.c_int,
                                               C.POINTER(C.c_float)]),
     "pclhip_icp_align": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(C.c_float),

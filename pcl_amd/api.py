@@ -2527,6 +2527,201 @@ class EuclideanClusterExtraction:
         return self._labels
 
 
+class RegionGrowing:
+    """pcl::RegionGrowing<PointT, NormalT> (segmentation/include/pcl/segmentation/region_growing.h:66-340,
+    impl/region_growing.hpp:231-548) over pclhip_region_growing: smooth mode, curvature test on, no residual test.  The
+    cloud is (n, c >= 3) float32, the normals (n, c >= 4) float32 = (nx, ny, nz, curvature), what NormalEstimation.compute()
+    returns; numpy or torch CUDA tensors.  The segments come back in the order their seeds were taken."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.p = _lib.RegionGrowingParams()
+        self.lib.pclhip_region_growing_params_default(C.byref(self.p))
+        self._min = int(self.p.min_cluster_size)
+        self._max = int(self.p.max_cluster_size)
+        self._tree = None
+        self._cloud = None
+        self._indices = None
+        self._normals = None
+        self._labels = None
+        self._last = None      # (offsets, indices) of the last extract
+        self._ms = 0.0
+
+    def getClassName(self):
+        return "RegionGrowing"
+
+    def setInputCloud(self, cloud):
+        self._cloud = cloud
+
+    def getInputCloud(self):
+        return self._cloud
+
+    def setIndices(self, indices):
+        """PCLBase::setIndices: only these records are segmented (None: every record)."""
+        self._indices = indices
+
+    def getIndices(self):
+        return self._indices
+
+    def setSearchMethod(self, tree):
+        self._tree = tree
+
+    def getSearchMethod(self):
+        return self._tree
+
+    def setInputNormals(self, normals):
+        self._normals = normals
+
+    def getInputNormals(self):
+        return self._normals
+
+    def setNumberOfNeighbours(self, k):
+        self.p.number_of_neighbours = int(k)
+
+    def getNumberOfNeighbours(self):
+        return int(self.p.number_of_neighbours)
+
+    def setSmoothnessThreshold(self, theta):
+        self.p.smoothness_threshold = float(theta)
+
+    def getSmoothnessThreshold(self):
+        return float(self.p.smoothness_threshold)
+
+    def setCurvatureThreshold(self, curvature):
+        self.p.curvature_threshold = float(curvature)
+
+    def getCurvatureThreshold(self):
+        return float(self.p.curvature_threshold)
+
+    def setMinClusterSize(self, n):
+        self._min = int(n)
+
+    def getMinClusterSize(self):
+        return self._min
+
+    def setMaxClusterSize(self, n):
+        self._max = int(n)
+
+    def getMaxClusterSize(self):
+        return self._max
+
+    def getSmoothModeFlag(self):
+        return True
+
+    def setSmoothModeFlag(self, value):
+        if not value:
+            raise NotImplementedError("RegionGrowing: only the smooth mode is built (the other tests every neighbour against "
+                                      "the initial seed's normal)")
+
+    def getCurvatureTestFlag(self):
+        return True
+
+    def setCurvatureTestFlag(self, value):
+        """region_growing.hpp:120-126: switching the curvature test off switches the residual test on."""
+        if not value:
+            raise NotImplementedError("RegionGrowing: without the curvature test the reference turns the residual test on, "
+                                      "which is not built (its result depends on the flood's order inside a region)")
+
+    def getResidualTestFlag(self):
+        return False
+
+    def setResidualTestFlag(self, value):
+        if value:
+            raise NotImplementedError("RegionGrowing: the residual test is not built (its result depends on the flood's "
+                                      "order inside a region)")
+
+    def setResidualThreshold(self, residual):
+        self.p.residual_threshold = float(residual)
+
+    def getResidualThreshold(self):
+        return float(self.p.residual_threshold)
+
+    def lastKernelMs(self):
+        """GPU time of the last extract() (all of its kernels)."""
+        return self._ms
+
+    def lastStats(self):
+        """dict(lists_ms, collapse_ms, phase1_ms, phase2_ms, phase1_rounds, phase2_rounds, unions, leftover) of the last
+        extract()."""
+        ms = [C.c_double(0.0) for _ in range(4)]
+        r1, r2, u, left = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self.lib.pclhip_index_last_region_growing_stats(self._tree.h, C.byref(ms[0]), C.byref(ms[1]), C.byref(ms[2]),
+                                                        C.byref(ms[3]), C.byref(r1), C.byref(r2), C.byref(u), C.byref(left))
+        return dict(lists_ms=ms[0].value, collapse_ms=ms[1].value, phase1_ms=ms[2].value, phase2_ms=ms[3].value,
+                    phase1_rounds=int(r1.value), phase2_rounds=int(r2.value), unions=int(u.value), leftover=int(left.value))
+
+    def _empty(self, n):
+        if _is_torch(self._cloud):
+            import torch
+            labels = torch.full((n,), -1, dtype=torch.int32, device=self._cloud.device)
+            idx = torch.empty(0, dtype=torch.int32, device=self._cloud.device)
+        else:
+            labels = np.full(n, -1, np.int32)
+            idx = np.empty(0, np.int32)
+        self._labels = labels
+        self._last = (np.zeros(1, np.uint64), idx)
+        self._ms = 0.0
+        return self._last[0], idx, labels
+
+    def extractCSR(self):
+        """-> (offsets uint64 [k + 1] (numpy), indices int32 [n_clustered], labels int32 [n]) of one call; indices and
+        labels are torch device tensors for a torch cloud.  No cloud, no normals, normals of another size or
+        number_of_neighbours == 0: no segment (prepareForSegmentation, region_growing.hpp:278-304)."""
+        n = 0 if self._cloud is None else int(self._cloud.shape[0])
+        if n == 0 or self._normals is None or int(self._normals.shape[0]) != n or self.p.number_of_neighbours == 0:
+            return self._empty(n)
+        if self._tree is None:
+            self._tree = KdTree(self.ctx)
+        key = (id(self._cloud), None if self._indices is None else id(self._indices))
+        if self._tree.h is None or self._tree._cloud_id != key:  # a tree built for another cloud or index set
+            self._tree.setInputCloud(self._cloud, self._indices)
+        assert self._normals.shape[1] >= 4, "the normals are (nx, ny, nz, curvature) records"
+        nptr, nstride, _, keep = _cloud(self._normals)
+        offsets = np.zeros(n + 1, np.uint64)
+        if _is_torch(self._cloud):
+            import torch
+            labels = torch.empty(n, dtype=torch.int32, device=self._cloud.device)
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=self._cloud.device)
+            lp, ip = C.c_void_p(labels.data_ptr()), C.c_void_p(idx.data_ptr())
+        else:
+            labels = np.empty(n, np.int32)
+            idx = np.empty(max(n, 1), np.int32)
+            lp, ip = C.c_void_p(labels.ctypes.data), C.c_void_p(idx.ctypes.data)
+        self.p.min_cluster_size = min(max(self._min, 0), 0xFFFFFFFF)
+        self.p.max_cluster_size = min(max(self._max, 0), 0xFFFFFFFF)
+        k, nc = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.pclhip_region_growing(self._tree.h, nptr, nstride, C.byref(self.p), lp,
+                                             offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n + 1, ip, n, C.byref(k),
+                                             C.byref(nc)), self.ctx.h)
+        del keep
+        self._ms = float(self.lib.pclhip_index_last_kernel_ms(self._tree.h))
+        self._labels = labels
+        self._last = (offsets[:k.value + 1], idx[:nc.value])
+        return self._last[0], self._last[1], labels
+
+    def extract(self):
+        """extract(std::vector<PointIndices>&): a list of ascending int32 index arrays."""
+        offsets, idx, _ = self.extractCSR()
+        off = offsets.astype(np.int64).tolist()
+        return [idx[off[c]:off[c + 1]] for c in range(len(off) - 1)]
+
+    def labels(self):
+        """Per record of the cloud: the number of its segment in the last extract(), -1 for a record in no returned one."""
+        return self._labels
+
+    def getSegmentFromPoint(self, index):
+        """The segment of the last extract() that holds record `index`; empty when it is in no returned segment.  (The
+        reference runs the segmentation if none has been run; so does this.)"""
+        if self._last is None:
+            self.extractCSR()
+        offsets, idx = self._last
+        lab = int(self._labels[int(index)]) if 0 <= int(index) < len(self._labels) else -1
+        if lab < 0:
+            return idx[:0]
+        return idx[int(offsets[lab]):int(offsets[lab + 1])]
+
+
 class SACSegmentation:
     """pcl::SACSegmentation<PointT> (segmentation/include/pcl/segmentation/sac_segmentation.h:77-330,
     impl/sac_segmentation.hpp:79-133,230-262) for SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE and SACMODEL_PARALLEL_PLANE

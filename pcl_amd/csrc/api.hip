@@ -1516,6 +1516,71 @@ void pclhip_index_last_cluster_stats(const pclhip_index* ix, double* hook_ms, do
   if (unions) *unions = ix ? ix->cluster_unions : 0;
 }
 
+// ---- RegionGrowing (region_growing.hpp) --------------------------------------------------------------
+void pclhip_region_growing_params_default(pclhip_region_growing_params* p) {
+  if (!p) return;
+  p->number_of_neighbours = 30;  // region_growing.h:282-323
+  p->smoothness_threshold = 30.0f / 180.0f * static_cast<float>(M_PI);
+  p->curvature_threshold = 0.05f;
+  p->curvature_test = 1;
+  p->smooth_mode = 1;
+  p->residual_test = 0;
+  p->residual_threshold = 0.05f;
+  p->min_cluster_size = 1;
+  p->max_cluster_size = UINT32_MAX;
+}
+
+pclhip_status pclhip_region_growing(pclhip_index* ix, const void* normals, size_t stride,
+                                    const pclhip_region_growing_params* prm, int32_t* out_labels, uint64_t* out_offsets,
+                                    uint64_t offsets_capacity, int32_t* out_indices, uint64_t indices_capacity,
+                                    uint64_t* n_clusters, uint64_t* n_clustered) {
+  if (!ix || !prm || !n_clusters || !n_clustered) return PCLHIP_ERR_INVALID;
+  pclhip_ctx* ctx = ix->ctx;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *n_clusters = 0;
+  *n_clustered = 0;
+  PCLHIP_REQUIRE(ctx, prm->residual_test == 0,
+                 "region growing: the residual test is not built (its result depends on the flood's order inside a region)");
+  PCLHIP_REQUIRE(ctx, prm->smooth_mode != 0,
+                 "region growing: only the smooth mode is built (the other tests against the initial seed's normal)");
+  PCLHIP_REQUIRE(ctx, prm->number_of_neighbours >= 0 && prm->number_of_neighbours <= 64,
+                 "region growing: number_of_neighbours must be 0 .. 64 (an edge mask is one 64-bit word)");
+  PCLHIP_REQUIRE(ctx, prm->smoothness_threshold == prm->smoothness_threshold, "the smoothness threshold must not be NaN");
+  PCLHIP_REQUIRE(ctx, normals != nullptr || ix->n_orig == 0, "null normals");
+  PCLHIP_REQUIRE(ctx, stride >= 16 && stride % 4 == 0, "stride must be a multiple of 4 and >= 16 bytes");
+  PCLHIP_REQUIRE(ctx, out_offsets == nullptr || !is_device_pointer(out_offsets), "out_offsets must be host memory");
+  if (ix->scaled) {
+    set_error(ctx, "region growing needs an index built in the cloud's own coordinates (no rescaling representation)");
+    return PCLHIP_ERR_STATE;
+  }
+  PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceGuard guard(ctx);
+  const void* dn = nullptr;
+  void* owned = nullptr;
+  if (ix->n_orig > 0) {
+    const pclhip_status st = to_device(ctx, normals, strided_span(ix->n_orig, stride, 16), &dn, &owned);
+    if (st != PCLHIP_OK) return st;
+    guard.add(owned);
+  }
+  // validatePoint (region_growing.hpp:469): float cosine_threshold = std::cos(theta_threshold_), a float argument
+  return region_growing(ix, dn, stride, prm->number_of_neighbours, cosf(prm->smoothness_threshold), prm->curvature_threshold,
+                        prm->curvature_test, prm->min_cluster_size, prm->max_cluster_size, out_labels, out_offsets,
+                        offsets_capacity, out_indices, indices_capacity, n_clusters, n_clustered);
+}
+
+void pclhip_index_last_region_growing_stats(const pclhip_index* ix, double* lists_ms, double* collapse_ms, double* phase1_ms,
+                                            double* phase2_ms, uint32_t* phase1_rounds, uint32_t* phase2_rounds,
+                                            uint64_t* unions, uint64_t* leftover) {
+  if (lists_ms) *lists_ms = ix ? ix->rg_ms[0] : 0.0;
+  if (collapse_ms) *collapse_ms = ix ? ix->rg_ms[1] : 0.0;
+  if (phase1_ms) *phase1_ms = ix ? ix->rg_ms[2] : 0.0;
+  if (phase2_ms) *phase2_ms = ix ? ix->rg_ms[3] : 0.0;
+  if (phase1_rounds) *phase1_rounds = ix ? ix->rg_rounds[0] : 0;
+  if (phase2_rounds) *phase2_rounds = ix ? ix->rg_rounds[1] : 0;
+  if (unions) *unions = ix ? ix->rg_unions : 0;
+  if (leftover) *leftover = ix ? ix->rg_leftover : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 void pclhip_icp_params_default(pclhip_icp_params* p) {
   if (!p) return;

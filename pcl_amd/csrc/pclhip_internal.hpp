@@ -306,6 +306,10 @@ struct pclhip_index {
   uint64_t boundary_pending = 0;    // ... and the queries its mask pass left to the resolve pass
   double cluster_ms[2] = {0, 0};    // the hook and the flatten kernel of the last pclhip_euclidean_clusters
   uint64_t cluster_unions = 0;      // ... and the unions its hook kernel attempted
+  double rg_ms[4] = {0, 0, 0, 0};   // the lists, the collapse and the two round loops of the last pclhip_region_growing
+  uint32_t rg_rounds[2] = {0, 0};   // ... the rounds of its two phases,
+  uint64_t rg_unions = 0;           // ... the unions its collapse attempted
+  uint64_t rg_leftover = 0;         // ... and the points it left to phase 2
   bool has_normals = false;
   bool scaled = false;              // built through a rescaling point representation: coordinates * scale
   bool subset = false;              // built with `indices`: it holds a selection of the cloud's records
@@ -609,6 +613,12 @@ pclhip_status boundary_compute(pclhip_index* ix, const int32_t* indices, uint64_
 pclhip_status euclidean_clusters(pclhip_index* ix, float t, uint32_t min_size, uint32_t max_size, int32_t* out_labels,
                                  uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices,
                                  uint64_t indices_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+// RegionGrowing over the index (region_growing.hpp, compiled into radius.hip): `normals` is a device pointer to the
+// strided (nx, ny, nz, curvature) records of the original cloud, cos_theta = cosf(smoothness threshold)
+pclhip_status region_growing(pclhip_index* ix, const void* normals, size_t stride, int k, float cos_theta, float curv_thr,
+                             int curvature_test, uint32_t min_size, uint32_t max_size, int32_t* out_labels,
+                             uint64_t* out_offsets, uint64_t offsets_capacity, int32_t* out_indices, uint64_t indices_capacity,
+                             uint64_t* n_clusters, uint64_t* n_clustered);
 // voxelgrid.hip's stable LSD radix passes (8 bits each) over n (key, value) pairs, ping-pong between (k0, v0) and (k1, v1);
 // iota: the values start as 0 .. n - 1.  Stream-ordered; the sorted arrays are one of the two pairs.
 pclhip_status radix_sort_pairs(pclhip_ctx* ctx, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, int bits,

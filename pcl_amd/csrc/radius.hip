@@ -446,6 +446,9 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 // EuclideanClusterExtraction: one radius traversal of the index whose hits are unions of a concurrent union-find
 #include "cluster.hpp"
 
+// RegionGrowing: k-NN lists, an edge mask per point, label propagation to the fixed point of the reference's flood
+#include "region_growing.hpp"
+
 // SACSegmentation (planes): batched RANSAC scoring, one pass over the points per batch of hypotheses
 #include "sac.hpp"
 // ... its constrained planes (a gate per hypothesis) and SACSegmentationFromNormals' plane (the distance with the normals)

@@ -1,0 +1,34 @@
+"""RegionGrowing in the CPU tier: the `-m gpu` tests of tests/test_gpu_region_growing.py and
+tests/test_gpu_region_growing_regimes.py run on the wavefront emulation of tests/wavesim (the recipe of
+tests/test_sac_models_wavesim.py).  Only the torch-buffer case and the case sized from the device's CU count stay on the
+GPU.  The emulation's workgroups run on host threads and its atomics are the host's, so the unions, the atomicMin rounds
+and the claims really race here."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from test_cluster_wavesim import on_the_emulation
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WS = os.path.join(ROOT, "tests", "wavesim")
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+GPU_ONLY = "not torch"
+
+
+@pytest.fixture(scope="module")
+def wavesim_lib():
+    if not os.path.exists(CLANG) or shutil.which("make") is None:
+        pytest.skip("needs the ROCm clang++ and make")
+    r = subprocess.run(["make", "-C", WS, "-j", str(min(16, os.cpu_count() or 1))], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return os.path.join(WS, "libpclhip_wavesim.so")
+
+
+def test_region_growing_gpu_tests_on_the_emulation(wavesim_lib):
+    on_the_emulation(wavesim_lib, "test_gpu_region_growing.py", GPU_ONLY)
+
+
+def test_region_growing_regimes_on_the_emulation(wavesim_lib):
+    on_the_emulation(wavesim_lib, "test_gpu_region_growing_regimes.py", GPU_ONLY + " and not fullgrid")
