@@ -360,6 +360,14 @@ PCLHIP_API void pclhip_index_last_iss_ms(const pclhip_index* index, double* scat
  * reference: the closed-form eigen33); non-finite records are neither queries nor neighbours and produce no output.  Not
  * built: the ORTHOGONAL projection (the reference's Newton loop, impl/mls.hpp:551-579, has no iteration cap), order > 2,
  * upsampling, setIndices, another search surface, cached MLS results.  Two calls give the same bytes.
+ * Accuracy of out_double against an exact evaluation of 1 .. 4 on the float inputs, with kappa = max(1, trace(C) / (l1 - l0),
+ * the condition number of the fit matrix with u, v in units of r) and away from kappa of about 1e10:
+ *   normal (up to sign), curvature   within (m + 32) * 2^-53 * kappa, wherever the cloud lies: every intermediate is kept
+ *                                    relative to q (p_j - q is exact in double, the call works with mean - q and adds q once)
+ *   point                            within (m + 32) * 2^-53 * kappa * r + 2 * 2^-53 * max(|q_x|, |q_y|, |q_z|): the second
+ *                                    term is the rounding of the final q + offset and of the value it is compared with; it
+ *                                    matters where |q| exceeds (m + 32) * kappa * r, as in a map frame
+ * The float outputs are out_double rounded once.
  * pclhip_index_last_kernel_ms gives the GPU time of the whole call, pclhip_index_last_mls_ms that of its two passes. */
 enum { PCLHIP_MLS_NONE = 0, PCLHIP_MLS_SIMPLE = 1, PCLHIP_MLS_ORTHOGONAL = 2 }; /* MLSResult::ProjectionMethod */
 PCLHIP_API pclhip_status pclhip_mls_process(pclhip_index* index, double search_radius, double sqr_gauss_param,

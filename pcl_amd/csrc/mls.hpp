@@ -15,6 +15,11 @@
 //      normal = normalize(n - coeff[3] u - coeff[1] v); otherwise point = mean, normal = n
 //   5. one record per surviving point: xyz, (normal, curvature), the original index -- floats -- and, when asked for, the
 //      unrounded doubles
+// Everything between the loads and the emit is RELATIVE TO THE QUERY: e_j = p_j - q (exact in double), the record holds
+// o = mean - q = ((sum e / m) . n) n, the fit's d is e_j - o, the fitted record o + coeff[0] n, and q is added once, in
+// mls_emit_kernel.  A mean stored at the point's own coordinates would be rounded at |q| (2^-40 at 8192) and hand every
+// neighbour of the fit that common error: far from the origin the normal then leaves its bound, which knows nothing of |q|.
+// The point itself cannot escape one rounding at |q|: its bound carries the term 2 * 2^-53 * max_i |q_i| (include/pclhip.h).
 // A positive radius whose float square is 0 gives every point an empty neighbourhood (fpfh.hpp's rule): no output, no
 // walk.
 //
@@ -22,15 +27,15 @@
 //   mls_plane_kernel   one lane per indexed point in kd order: m, sum d and the six sums of d d^T over the hits of every
 //                      staged leaf (d = p_j - q widened before the subtraction: |d| < r, so the one-pass form
 //                      C = sum d d^T - (sum d)(sum d)^T / m loses nothing), then a cyclic Jacobi on named scalars that
-//                      carries the rotation.  Writes the plane record (mean, n, curvature, m: 8 doubles) by kd position
+//                      carries the rotation.  Writes the plane record (mean - q, n, curvature, m: 8 doubles) by kd position
 //                      and the survivor flag by ORIGINAL index.  One writer per slot, no atomics.
 //   mls_fit_kernel     the same walk again for the lanes with m >= 6 (a group of 64 without one is skipped): the 15
 //                      moments sum w u^a v^b (a + b <= 4) and the 6 moments sum w f u^a v^b (a + b <= 2), from which the
 //                      6 x 6 system is assembled (the reference's P diag(w) P^T up to summation order); Cholesky and the
 //                      two triangular solves on constant indices.  A fitted lane overwrites its own record with the
-//                      projected point and normal.  Not launched for order < 2 or the method NONE.
+//                      projected point (less q) and normal.  Not launched for order < 2 or the method NONE.
 //   scan (device_scan.hpp) + mls_emit_kernel   stable compaction in original-index order, no atomic ticket; kd order ->
-//                      original order through the index's rank array
+//                      original order through the index's rank array; point = q + the record's offset
 // Both walks are traverse<Policy, true> with a fixed bound inside for_each_query_group: the order of the sums is a function
 // of the index alone, two calls give the same bytes.  No wave waits for another; the Jacobi sweeps are capped.
 //
@@ -56,7 +61,7 @@
 namespace pclhip {
 namespace {
 
-constexpr int MLS_REC = 8;  // doubles per record: point / mean (3), normal (3), curvature, m
+constexpr int MLS_REC = 8;  // doubles per record: point / mean less the query (3), normal (3), curvature, m
 
 // Pass 1: the neighbour count, the sum of d = p_j - q and the six sums of d d^T
 struct MlsPlane {
@@ -188,11 +193,11 @@ __global__ __launch_bounds__(OR_BLOCK) void mls_plane_kernel(IndexView ix, float
     const double trace = a00 + a11 + a22;
     double l0, nx, ny, nz;
     mls_smallest_eigenpair(a00, a01, a02, a11, a12, a22, l0, nx, ny, nz);
-    // q - c = -(sum d) / m
+    // q - c = -(sum d) / m; the record keeps o = mean - q: q, and with it the rounding at |q|, joins in mls_emit_kernel
     const double dist = -(pol.sx / m * nx + pol.sy / m * ny + pol.sz / m * nz);
-    r[0] = pol.px - dist * nx;
-    r[1] = pol.py - dist * ny;
-    r[2] = pol.pz - dist * nz;
+    r[0] = -dist * nx;
+    r[1] = -dist * ny;
+    r[2] = -dist * nz;
     r[3] = nx;
     r[4] = ny;
     r[5] = nz;
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(OR_BLOCK) void mls_plane_kernel(IndexView ix, float
 struct MlsFit {
   float t;
   uint32_t n;
-  double mx, my, mz;  // mean
+  double mx, my, mz;  // o = mean - q
   double nx, ny, nz, ux, uy, uz, vx, vy, vz;
   double inv_sg;
   double m00, m01, m02, m03, m04, m10, m11, m12, m13, m20, m21, m22, m30, m31, m40;
@@ -224,9 +229,10 @@ struct MlsFit {
     while (mask != 0) {
       const uint32_t j = uint32_t(__builtin_ctz(mask));
       mask &= mask - 1u;
-      const double dx = double(leaf_coord<16>(s, 0, j)) - mx;
-      const double dy = double(leaf_coord<16>(s, 1, j)) - my;
-      const double dz = double(leaf_coord<16>(s, 2, j)) - mz;
+      // p_j - q is exact in double (two floats); a mean rounded at |q| never enters: a cloud at 8192 keeps its bound
+      const double dx = (double(leaf_coord<16>(s, 0, j)) - double(qx[0])) - mx;
+      const double dy = (double(leaf_coord<16>(s, 1, j)) - double(qy[0])) - my;
+      const double dz = (double(leaf_coord<16>(s, 2, j)) - double(qz[0])) - mz;
       const double w = exp(-(dx * dx + dy * dy + dz * dz) * inv_sg);
       const double u = dx * ux + dy * uy + dz * uz;
       const double v = dx * vx + dy * vy + dz * vz;
@@ -346,9 +352,11 @@ __global__ __launch_bounds__(OR_BLOCK) void mls_fit_kernel(IndexView ix, float t
 }
 
 // the records of the ids i with flag[i] != 0, ascending (excl: exclusive scan of flag), kd order -> original order by rank;
-// what does not fit the caller's capacity is dropped
+// what does not fit the caller's capacity is dropped.  The record's offset o (or o + coeff[0] n) becomes the point here:
+// q + offset, the one operation of the call that rounds at |q|
 __global__ __launch_bounds__(OR_BLOCK) void mls_emit_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ excl,
                                                             const uint32_t* __restrict__ rank, uint64_t n_orig,
+                                                            const float4* __restrict__ pts,
                                                             const double* __restrict__ rec, float* __restrict__ out_points,
                                                             float* __restrict__ out_normals, int32_t* __restrict__ out_indices,
                                                             double* __restrict__ out_double, uint64_t capacity) {
@@ -356,10 +364,13 @@ __global__ __launch_bounds__(OR_BLOCK) void mls_emit_kernel(const uint32_t* __re
   if (i >= n_orig || flag[i] == 0u) return;
   const uint64_t e = excl[i];
   if (e >= capacity) return;
-  const double* r = rec + size_t(rank[i]) * MLS_REC;
+  const uint32_t pos = rank[i];
+  const double* r = rec + size_t(pos) * MLS_REC;
+  const float4 q = pts[pos];
+  const double point[3] = {double(q.x) + r[0], double(q.y) + r[1], double(q.z) + r[2]};
   if (out_points != nullptr) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out_points[e * 3 + k] = float(r[k]);
+    for (int k = 0; k < 3; ++k) out_points[e * 3 + k] = float(point[k]);
   }
   if (out_normals != nullptr) {
 #pragma unroll
@@ -368,7 +379,7 @@ __global__ __launch_bounds__(OR_BLOCK) void mls_emit_kernel(const uint32_t* __re
   if (out_indices != nullptr) out_indices[e] = int32_t(i);
   if (out_double != nullptr) {
 #pragma unroll
-    for (int k = 0; k < MLS_REC; ++k) out_double[e * MLS_REC + k] = r[k];
+    for (int k = 0; k < MLS_REC; ++k) out_double[e * MLS_REC + k] = k < 3 ? point[k] : r[k];
   }
 }
 
@@ -427,8 +438,8 @@ pclhip_status mls_process(pclhip_index* ix, float t, double sqr_gauss_param, boo
     if (out_normals != nullptr && !nrm_dev) PCLHIP_CHECK_HIP(ctx, scope.alloc(&d_nrm, size_t(cap) * 16));
     if (out_indices != nullptr && !idx_dev) PCLHIP_CHECK_HIP(ctx, scope.alloc(&d_idx, size_t(cap) * 4));
     if (out_double != nullptr && !dbl_dev) PCLHIP_CHECK_HIP(ctx, scope.alloc(&d_dbl, size_t(cap) * MLS_REC * 8));
-    hipLaunchKernelGGL(mls_emit_kernel, or_blocks(n_orig), dim3(OR_BLOCK), 0, s, flag, excl, ix->rank, n_orig, rec, d_pts, d_nrm,
-                       d_idx, d_dbl, cap);
+    hipLaunchKernelGGL(mls_emit_kernel, or_blocks(n_orig), dim3(OR_BLOCK), 0, s, flag, excl, ix->rank, n_orig, v.pts, rec, d_pts,
+                       d_nrm, d_idx, d_dbl, cap);
     PCLHIP_CHECK_HIP(ctx, hipGetLastError());
   }
   (void)hipEventRecord(e3, s);

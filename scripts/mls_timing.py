@@ -4,10 +4,13 @@ time of pclhip_mls_process (whole call, and its two kernels) and the time of the
 offered before it: pclhip_radius_search of the cloud against itself into device memory, then the centroid and covariance
 sums, a batched torch.linalg.eigh, the weighted normal equations and torch.cholesky_solve in float64 on the device, chunked
 to fit memory.  The baseline is that composition; counts and indices must be equal and the points must agree within the
-bound of tests/mls_restatement.py, (m + 32) * 2^-53 * kappa * r, outside its excluded records.  Writes
+bound of tests/mls_restatement.py, (m + 32) * 2^-53 * kappa * r + far_point_term, outside its excluded records.  Writes
 profiles/mls_timing.json (and prints it).
 
-    python scripts/mls_timing.py [n] [--radius R]
+    python scripts/mls_timing.py [n] [--radius R] [--compare-lib OTHER/libpclhip.so]
+
+With --compare-lib the fused step also runs with PCLHIP_LIB set to that library, three rounds in alternation with this
+build, each a process of its own: "fit_pass_ab" holds both builds' pass times per round, medians and spreads.
 
 Each GPU step runs as a child process under its own `timeout`; the first failure ends the run.  A comparison that misses
 (counts, indices, m, or a difference beyond the bound) does not: its figures are written with "ok": false and the script
@@ -25,16 +28,17 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 STEP_TIMEOUT_S = {"fused": 240, "composition": 900}
+AB_ROUNDS = 3                  # --compare-lib: alternating rounds per build
 PEAK_BYTES_PER_S = 8.0e12      # HBM3E of the MI355X
 PEAK_FP64_FLOPS = 78.6e12      # vector fp64 of AMD's specification
 U = 2.0 ** -53
 ALLOWANCE = 32                 # tests/mls_restatement.py: SOLVER_ALLOWANCE
 # fp64 operations per pair, counted from pcl_amd/csrc/mls.hpp (an fma is 2): the plane walk widens and subtracts (3), adds
-# the three sums (3) and six fmas (12); the fit walk subtracts (3), d.d (5) and the scale (1), three dot products (15), ten
+# the three sums (3) and six fmas (12); the fit walk subtracts twice (6: the query, then mean - q), d.d (5) and the scale (1), three dot products (15), ten
 # products (10), ten adds and five fmas of the u, v moments (20), one add and five fmas and three products of the f moments
 # (14) -- and one exp
 FLOPS_PLANE_PER_PAIR = 18
-FLOPS_FIT_PER_PAIR = 68
+FLOPS_FIT_PER_PAIR = 71
 
 
 def setup(n):
@@ -199,19 +203,26 @@ def step_composition(n, r):
         dn = torch.minimum((d_dbl[:, 3:6] - normal[rows]).abs().amax(dim=1), (d_dbl[:, 3:6] + normal[rows]).abs().amax(dim=1))
         dc = (d_dbl[:, 6] - curv[rows]).abs()
         bu = bound_unit[rows]
+        # the point's bound carries tests/mls_restatement.py's far_point_term, 2 * 2^-53 * max_i |q_i|: the rounding of the
+        # final q + offset, once per implementation
+        far = 2.0 * U * q64[rows].abs().amax(dim=1)
+        bp = bu * r + far
         cmp.update({"excluded": int((~live).sum()), "fitted": int(fitted[rows].sum()),
                     "m_equal": bool((d_dbl[:, 7] == m[rows].double()).all()),
-                    "worst_point_over_bound": float((dp / (bu * r))[live].max()),
+                    "worst_point_over_bound": float((dp / bp)[live].max()),
+                    "worst_point_over_bound_without_the_point_term": float((dp / (bu * r))[live].max()),
                     "worst_normal_over_bound": float((dn / bu)[live].max()),
                     "worst_curvature_over_bound": float((dc / bu)[live].max()),
                     "largest_point_difference": float(dp[live].max())})
         # for the record: the same differences in units of 2^-53 times the point's largest coordinate, one rounding of a double
-        # at the point -- the bound scales with r and knows nothing of |q|; where (m + 32) * kappa * r < |q| it lies below that
+        # at the point, and how many points the bound without the point term would have missed
         one = U * point[rows].abs().amax(dim=1)
-        late = dp / (bu * r) > 1.0
+        late = dp / bp > 1.0
+        bare = dp / (bu * r) > 1.0
         cmp.update({"largest_point_difference_in_roundings_at_the_point": float((dp / one)[live].max()),
                     "points_beyond_the_bound": int((late & live).sum()),
-                    "largest_bound_over_rounding_among_them": float(((bu * r) / one)[late & live].max()) if bool((late & live).any()) else None,
+                    "points_beyond_the_bound_without_the_point_term": int((bare & live).sum()),
+                    "largest_bound_over_rounding_among_them": float((bp / one)[late & live].max()) if bool((late & live).any()) else None,
                     "median_point_bound": float((bu * r)[live].median()),
                     "largest_coordinate": float(point[rows].abs().max())})
     out["neighbours_per_point"] = round((pairs - n) / n, 3)
@@ -233,6 +244,9 @@ def main():
     ap.add_argument("--radius", type=float, default=0.001954, help="the search radius")
     ap.add_argument("--step", choices=tuple(STEP_TIMEOUT_S), default=None, help="run one step in this process")
     ap.add_argument("--out", default=None, help="with --step: where the step's JSON goes")
+    ap.add_argument("--compare-lib", default=None, help="another build of the library (say, the parent commit's): its fused "
+                    "step runs in alternation with this build's and both builds' pass times are recorded")
+    ap.add_argument("--compare-label", default="parent commit", help="what --compare-lib is, for the record")
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "mls_timing.json"), help="where the result goes")
     a = ap.parse_args()
     n, r = a.n, a.radius
@@ -262,6 +276,29 @@ def main():
             status = status or rc
             with open(piece) as f:
                 out.update(json.load(f))
+        if a.compare_lib:  # the fused step of both builds in alternation, a process each: medians of five calls per round
+            arms = (("this_build", None), ("other_build", os.path.abspath(a.compare_lib)))
+            rounds = {arm: [] for arm, _ in arms}
+            for rnd in range(AB_ROUNDS):
+                for arm, lib in arms:
+                    piece = os.path.join(tmp, "%s_%d.json" % (arm, rnd))
+                    cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S["fused"]), sys.executable, os.path.abspath(__file__), str(n),
+                           "--radius", repr(r), "--step", "fused", "--out", piece]
+                    rc = subprocess.call(cmd, env=dict(os.environ, PCLHIP_LIB=lib) if lib else None)
+                    if rc != 0:
+                        print("A/B round %d of %s failed with status %d: stopping" % (rnd, arm, rc), file=sys.stderr)
+                        return rc
+                    with open(piece) as f:
+                        rounds[arm].append(json.load(f)["fused"])
+            ab = {"rounds": AB_ROUNDS, "other_build": a.compare_label}
+            for arm, _ in arms:
+                for key in ("fit_ms", "plane_ms", "call_gpu_ms"):
+                    vals = sorted(x[key] for x in rounds[arm])
+                    ab["%s_%s" % (arm, key)] = {"per_round": [x[key] for x in rounds[arm]], "median": vals[len(vals) // 2],
+                                                "spread": round((vals[-1] - vals[0]) / vals[len(vals) // 2], 4)}
+            ab["same_records"] = len({(x["records"], x["checksum"]) for arm, _ in arms for x in rounds[arm]}) == 1
+            ab["fit_ms_this_over_other"] = round(ab["this_build_fit_ms"]["median"] / ab["other_build_fit_ms"]["median"], 4)
+            out["fit_pass_ab"] = ab
     fused, comp = out["fused"], out["composition_radius_search_torch"]
     out["speedup_call_vs_composition"] = round(comp["gpu_ms"] / fused["call_gpu_ms"], 2)
     out["pairs_per_second_plane"] = round(out["pairs"] / (fused["plane_ms"] * 1e-3), 0)

@@ -22,8 +22,15 @@ m * 2^-53 bounds a sequential sum of m terms in any order, kappa carries it thro
 the solve (cond), and A allows for the two eigen solvers, the Cholesky and the exp.  A record whose point bound exceeds
 1e-3 * r (kappa of about 1e10) is `excluded`: its answer is not determined by the data.
 
+Far from the origin.  Those bounds scale with r and know nothing of |q|.  Normal and curvature are functions of coordinate
+differences and keep their bound wherever the cloud lies -- provided the implementation keeps its intermediates relative to
+the query (query_relative=True: e = p_j - q exactly, o = mean - q, d = e - o, q added once).  The default formulations here
+follow the reference and subtract a mean that was rounded at |q|; at |q| = 8192 their normals leave the bound sixfold
+(tests/test_far_clouds_restatement.py).  The point cannot avoid one rounding at |q|: far_point_term() = 2 * 2^-53 * max_i |q_i|
+joins bound_point wherever a point is compared far out (one half-ulp of the final q + offset per implementation).
+
 A = SOLVER_ALLOWANCE is set from this restatement ALONE (spread(): 8 random neighbour orders, two-pass against one-pass shifted
-sums, matrix product against moments), never from a run of the device code: it stays at iss_restatement's 32 while the
+sums, matrix product against moments, the query-relative formulation in the second half of the orders), never from a run of the device code: it stays at iss_restatement's 32 while the
 measured spread stays within a quarter of the bound.  Measured worst |d| / bound over the clouds of
 tests/test_mls_restatement.py::test_order_spread_sets_the_allowance: see MEASURED_WORST_SPREAD below."""
 import os
@@ -37,7 +44,13 @@ F32 = np.float32
 U = 2.0 ** -53
 SOLVER_ALLOWANCE = 32
 SPREAD_CAP = 0.25              # A stays 32 while the restatement's own spread stays within this share of the bound
-MEASURED_WORST_SPREAD = 0.1881  # (a point of bun0 at r = 0.0075; 0.1411 at r = 0.01, 0.0035 at r = 0.03) the worst |d| / bound that test_order_spread_sets_the_allowance printed
+MEASURED_WORST_SPREAD = 0.1881  # (a point of bun0 at r = 0.0075; 0.1411 at r = 0.01, 0.0035 at r = 0.03) the worst |d| / bound that test_order_spread_sets_the_allowance printed for the formulations that subtract a mean
+# With the query-relative formulation in spread()'s rotation the same test prints 0.2489: its POINT at bun0 r = 0.0075 against
+# bound_point + far_point_term -- the point moved by 2.78e-17, one ulp of a double at |q| = 0.19; normals at most 0.0549,
+# curvatures 0.0214.  Far from the origin (tests/test_far_clouds_restatement.py, the 2^-10 grid moved by (8192, -8192, 4096)
+# against the unmoved restatement plus the shift), worst |d| / bound of the query-relative formulation:
+MEASURED_FAR_QUERY_RELATIVE = {0.1: (0.0000, 0.0008, 0.0008), 0.06: (0.8101, 0.0074, 0.0016)}  # r -> (point with far_point_term, normal, curvature)
+# and of the two that subtract a mean rounded at |q|: normal 5.878 at r = 0.1 and 6.361 at r = 0.06 (both), point 0.989 / 0.994
 NONE, SIMPLE, ORTHOGONAL = 0, 1, 2
 
 # the reference's own test (test/surface/test_moving_least_squares.cpp:95-118): record 0 of bun0 at r = 0.03, order 2
@@ -101,9 +114,12 @@ def fit_system(uj, vj, fj, w, moments):
     return A, np.array([fm[t] for t in TERMS])
 
 
-def one_point(q, nb, radius, sqr_gauss_param, order, method, one_pass=False, moments=False):
-    """q [3] float64, nb [m, 3] float64 (m >= 3) in the order the sums are to run -> dict of the record"""
+def one_point(q, nb, radius, sqr_gauss_param, order, method, one_pass=False, moments=False, query_relative=False):
+    """q [3] float64, nb [m, 3] float64 (m >= 3) in the order the sums are to run -> dict of the record.  query_relative: the
+    formulation that never subtracts a value rounded at the point's coordinates (the module's docstring)"""
     m = len(nb)
+    if query_relative:
+        return one_point_query_relative(q, nb, radius, sqr_gauss_param, order, method, moments)
     if one_pass:  # shifted by the query: C = sum d d^T - (sum d)(sum d)^T / m
         d = nb - q
         s = d.sum(axis=0)
@@ -142,8 +158,53 @@ def one_point(q, nb, radius, sqr_gauss_param, order, method, one_pass=False, mom
     return rec
 
 
+def one_point_query_relative(q, nb, radius, sqr_gauss_param, order, method, moments=False):
+    """one_point with every intermediate relative to the query: e = p_j - q (exact in float64 for float32 inputs within a
+    factor 2^29 of each other), C = sum e e^T - (sum e)(sum e)^T / m, o = mean - q = ((sum e / m) . n) n, the fit's
+    d = e - o, and q is added ONCE, to o or to o + coeff[0] n"""
+    m = len(nb)
+    e = nb - q
+    s = e.sum(axis=0)
+    C = e.T @ e - np.outer(s, s) / m
+    C = (C + C.T) / 2
+    w, V = np.linalg.eigh(C)
+    trace = C[0, 0] + C[1, 1] + C[2, 2]
+    n = sign_rule(V[:, 0] / np.linalg.norm(V[:, 0]))
+    o = np.dot(s / m, n) * n  # q - c = -(sum e) / m
+    curvature = abs(w[0] / trace) if trace != 0 else 0.0
+    gap = (w[1] - w[0]) / trace if trace > 0 else 0.0
+    rec = dict(m=m, plane_point=q + o, plane_normal=n, curvature=curvature, gap=gap, cond=1.0, fitted=False, point=q + o,
+               normal=n)
+    if order == 2 and m >= 6:
+        v = unit_orthogonal(n)
+        u = np.cross(n, v)
+        d = e - o
+        wt = np.exp(-np.einsum("ij,ij->i", d, d) / sqr_gauss_param)
+        uj, vj, fj = d @ u, d @ v, d @ n
+        A, rhs = fit_system(uj, vj, fj, wt, moments)
+        coeff = cholesky_solve(A, rhs)
+        if coeff is not None and np.isfinite(coeff[0]):
+            rec["fitted"] = True
+            scale = float(radius) ** -DEGREE.astype(np.float64)
+            As = A * scale[:, None] * scale[None, :]
+            rec["cond"] = float(np.linalg.cond(As)) if np.isfinite(As).all() else np.inf
+            if method == SIMPLE:
+                rec["point"] = q + (o + coeff[0] * n)
+                t = n - coeff[3] * u - coeff[1] * v
+                rec["normal"] = t / np.linalg.norm(t)
+    return rec
+
+
+def far_point_term(points, indices):
+    """per output record: 2 * 2^-53 * max_i |q_i| -- each of two correct implementations rounds its final q + offset once, to
+    half an ulp (at most 2^-53 |value|) of a value of the magnitude of q.  A derived rounding bound that joins bound_point
+    where clouds lie far from the origin; it is no allowance, SPREAD_CAP does not govern it."""
+    q = np.asarray(points, F32)[np.asarray(indices, np.int64), :3].astype(np.float64)
+    return 2.0 * U * np.abs(q).max(axis=1) if len(q) else np.zeros(0)
+
+
 def restate(points, radius, sqr_gauss_param=None, order=2, method=SIMPLE, rows=None, rng=None, one_pass=False,
-            moments=False):
+            moments=False, query_relative=False):
     """-> dict over the k output records (those of `rows`, default every record, with m >= 3, ascending): indices int32, m,
     point / normal / plane_point / plane_normal [k, 3], curvature, fitted, gap, cond, kappa, bound_point, bound_unit,
     excluded; and m_all [len(rows)].  rng: the neighbours in a random order instead of ascending distance."""
@@ -168,7 +229,7 @@ def restate(points, radius, sqr_gauss_param=None, order=2, method=SIMPLE, rows=N
                 dd = pts[nb] - pts[i]
                 d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
             nb = nb[np.argsort(d2, kind="stable")] if rng is None else nb[rng.permutation(len(nb))]
-            recs.append(one_point(p64[i], p64[nb], radius, sqr_gauss_param, order, method, one_pass, moments))
+            recs.append(one_point(p64[i], p64[nb], radius, sqr_gauss_param, order, method, one_pass, moments, query_relative))
             ids.append(i)
     k = len(recs)
     vec = lambda key: np.array([x[key] for x in recs], np.float64).reshape(k, 3)  # noqa: E731
@@ -192,21 +253,27 @@ def normal_delta(a, b):
 def spread(points, radius, sqr_gauss_param=None, orders=8, seed=0):
     """the restatement against itself: the neighbours in `orders` random orders, in both formulations of the plane sums and of
     the fit matrix -> the worst |d| / bound over the records that are not excluded (point, normal, curvature), the largest
-    absolute moves (point, normal) and the base restatement"""
+    absolute moves (point, normal) and the base restatement.  The second half of the orders runs the query-relative
+    formulation (with either fit matrix); its point -- q + offset, where the others form q - ... and mean + ... -- is held to
+    bound_point + far_point_term: the last rounding at |q| is that term's, a derived bound, and no business of the allowance.
+    Normal and curvature of every formulation, and the point of the others, are held to the bounds with A alone."""
     base = restate(points, radius, sqr_gauss_param)
     keep = ~base["excluded"]
+    far = far_point_term(points, base["indices"])
     worst = np.zeros(3)
     moved = np.zeros(2)
     rng = np.random.default_rng(seed)
     for t in range(orders):
-        other = restate(points, radius, sqr_gauss_param, rng=rng, one_pass=bool(t & 1), moments=bool(t & 2))
+        other = restate(points, radius, sqr_gauss_param, rng=rng, one_pass=bool(t & 1), moments=bool(t & 2),
+                        query_relative=bool(t & 4))
         assert np.array_equal(other["indices"], base["indices"]) and np.array_equal(other["m"], base["m"])
         assert np.array_equal(other["fitted"][keep], base["fitted"][keep])
         dp = np.abs(other["point"] - base["point"]).max(axis=1)[keep]
         dn = normal_delta(other["normal"], base["normal"])[keep]
         dc = np.abs(other["curvature"] - base["curvature"])[keep]
         if keep.any():
-            worst = np.maximum(worst, [(dp / base["bound_point"][keep]).max(), (dn / base["bound_unit"][keep]).max(),
+            bp = (base["bound_point"] + far if t & 4 else base["bound_point"])[keep]
+            worst = np.maximum(worst, [(dp / bp).max(), (dn / base["bound_unit"][keep]).max(),
                                        (dc / base["bound_unit"][keep]).max()])
             moved = np.maximum(moved, [dp.max(), dn.max()])
     return worst, moved, base
