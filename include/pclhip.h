@@ -603,6 +603,106 @@ PCLHIP_API double pclhip_icp_last_median_distance(const pclhip_icp* icp);
  * when the source is cut into slabs. */
 PCLHIP_API pclhip_status pclhip_icp_set_reciprocal(pclhip_icp* icp, int enable);
 
+/* ---- CorrespondenceRejectorSampleConsensus: RANSAC over a rigid transform ------------------------------
+ * Replaces pcl::registration::CorrespondenceRejectorSampleConsensus<PointT>::getRemainingCorrespondences
+ * (registration/include/pcl/registration/impl/correspondence_rejection_sample_consensus.hpp:55-142) with
+ * SampleConsensusModelRegistration (sample_consensus/.../impl/sac_model_registration.hpp:48-97,203-249,289-322,
+ * sac_model_registration.h:264-289, sac_model.h:162-197) under RandomSampleConsensus (impl/ransac.hpp:56-217).
+ * Input: n correspondences (index_query[j], index_match[j]) over a source and a target cloud; samples, inliers and the
+ * trace speak of list positions j.  In the chain of pclhip_icp_set_rejectors (kind PCLHIP_REJ_SAMPLE_CONSENSUS) the list is
+ * the pairs still kept, in ascending original query index, over the MOVED source (impl/icp.hpp:192-193).
+ * Sample distance threshold (sac_model_registration.h:264-289): the nine sums of computeMeanAndCovarianceMatrix over the
+ * list's finite source points (shifted by the list's first source point when that is finite) in double in a fixed order
+ * that depends on n alone, the covariance formed in double and rounded once to float, pcl::eigen33's eigenvalues in the
+ * reference's float order, sample_dist_thresh = (float(sqrtf(l0) + sqrtf(l1) + sqrtf(l2)) / 3.0)^2 in double.  A NaN
+ * threshold (a negative eigenvalue) makes every sample bad: no model, as in the reference.
+ * Trial t = 0, 1, 2, ... (sac_model.h:162-197): attempt a = 0 .. 999 draws three distinct list positions -- draw j is
+ * int((n - j) * u) with u from the keyed splitmix of scp_draw.hpp over (seed, trial, attempt, slot j), placed by
+ * insert_samples -- and uses them in ascending order; the sample is good (isSampleGood, :48-66) when each of the three
+ * float squared edge lengths (dx dx + dy dy) + dz dz of its SOURCE points, as a double, exceeds sample_dist_thresh.  The
+ * first good attempt is the trial's sample; a trial whose 1,000 attempts all fail ends the loop there ("No samples could
+ * be selected", ransac.hpp:120-124).  n < 3: no model.
+ * Hypothesis: pcl::umeyama(src, tgt, false) of the three pairs in double on the demeaned points, rounded once to a float
+ * 4x4 T with last row (0, 0, 0, 1) (the routine of SampleConsensusPrerejective above).
+ * Score (countWithinDistance / selectWithinDistance, :203-249): in float without contraction
+ *   p.x = ((T00 s.x + T01 s.y) + T02 s.z) + T03 (y, z alike), e = p - t, d2 = (e.x e.x + e.z e.z) + e.y e.y;
+ * the pair is an inlier iff double(d2) < threshold * threshold (a double product).  A non-finite point is never an inlier.
+ * Counting and selecting use this one expression.
+ * Stopping rule (ransac.hpp:154-201, sac_replay.hpp's without its skip branch), trials in order: a count > best (strict:
+ * the earliest wins) becomes the model and sets k = log(1 - probability) / log(clamp(1 - (best / n)^3, DBL_EPSILON,
+ * 1 - DBL_EPSILON)); ++iterations; the loop ends when iterations > k or iterations > max_iterations.
+ * Result: without a trial whose count is above 0, or when the winner selects fewer than 3 pairs, the whole list remains
+ * and the best transformation is the identity (:101-119); otherwise the winner's inliers remain, in the list's order
+ * (:120-127), and the best transformation is the winner's T.  Two calls give the same bytes; batch_size never changes a
+ * result; the chain's result is the standalone call's on the same list.
+ * Deviations: the draws (the reference's rand() sequence; its samples are used in draw order); one float order without
+ * contraction where the reference leaves the order of the 4x4 product and of squaredNorm to Eigen; the covariance sums
+ * are double tree sums rounded once (the reference adds in float); the loop is replayed on the device, so the stopping
+ * rule's log and pow are the device's; duplicate query indices in a standalone list are refused (the reference's map
+ * silently keeps the last one).
+ * Refused: refine != 0 (refineModel is a host loop of up to 1,000 data-dependent rounds with a median per round:
+ * PCLHIP_ERR_INVALID with a message); duplicate query indices and indices outside a cloud (PCLHIP_ERR_INVALID);
+ * max_iterations above 1,000,000 or negative, a threshold that is negative or NaN, a probability outside ]0, 1[
+ * (PCLHIP_ERR_INVALID); the chain kind under multi-GPU iterations (PCLHIP_ERR_STATE).  Not built:
+ * CorrespondenceRejectorSampleConsensus2D.
+ *
+ * In the chain: pclhip_rejector.param = inlier threshold, .min_correspondences = max_iterations, .reserved = seed;
+ * probability 0.99 (the class has no setter).  Kinds 0..3 ignore `reserved` as before. */
+enum { PCLHIP_REJ_SAMPLE_CONSENSUS = 4 };
+typedef struct {
+  double inlier_threshold;          /* correspondence_rejection_sample_consensus.h: default 0.05 */
+  int max_iterations;               /* default 1000 */
+  double probability;               /* default 0.99 */
+  uint64_t seed;                    /* of the draws, default 0 */
+  int batch_size;                   /* trials per scoring pass (<= 1024); 0 (default): 16 first, then doubling */
+  int refine;                       /* setRefineModel: must be 0 */
+} pclhip_rejector_sac_params;
+typedef struct {
+  uint64_t trials;                  /* trials the replay consumed */
+  int iterations;                   /* iterations_ */
+  int best_trial;                   /* the trial with the highest count; -1: none had a count above 0 */
+  uint32_t best_count;              /* its count */
+  uint32_t remaining;               /* pairs that remain (n without a model) */
+  int has_model;                    /* 1: the winner's inliers remain; 0: the list is unchanged, T is the identity */
+  int no_sample;                    /* 1: the loop ended at a trial whose 1,000 attempts found no good sample */
+  uint32_t n;                       /* length of the list */
+  uint32_t reserved;
+  double sample_dist_thresh;
+} pclhip_rejector_sac_stats;
+typedef struct {                    /* one entry per consumed trial (pclhip_rejector_sac_last_trace) */
+  int samples[3];                   /* ascending list positions (the last attempt's) */
+  int attempts;                     /* draws of three made: 1 .. 1000 */
+  int no_sample;                    /* 1: none of them was good (the transformation is zero, the count 0) */
+  float transformation[16];
+  uint32_t count;
+} pclhip_rejector_sac_trace;
+PCLHIP_API void pclhip_rejector_sac_params_default(pclhip_rejector_sac_params* p);
+/* Clouds (records of stride bytes, xyz first) and lists (int32) may be host or device memory.  out_positions (optional,
+ * host or device, `capacity` entries): the list positions that remain, ascending (getInliersIndices); *out_n (host) is
+ * always written, a capacity that is too small gives PCLHIP_ERR_OVERFLOW after it.  out_T (optional, host): the best
+ * transformation, row-major.  out_stats optional. */
+PCLHIP_API pclhip_status pclhip_correspondence_rejector_sample_consensus(
+    pclhip_ctx* ctx, const void* source, uint64_t n_source, size_t source_stride_bytes, const void* target,
+    uint64_t n_target, size_t target_stride_bytes, const int32_t* index_query, const int32_t* index_match, uint64_t n,
+    const pclhip_rejector_sac_params* params, int32_t* out_positions, uint64_t capacity, uint64_t* out_n, float out_T[16],
+    pclhip_rejector_sac_stats* out_stats);
+/* countWithinDistance of n_models row-major 4x4 transforms (host; rows 0..2 are used): out_counts[m] (host) pairs of the
+ * list with double(d2) < threshold * threshold (exposed for tests). */
+PCLHIP_API pclhip_status pclhip_rejector_sac_evaluate(pclhip_ctx* ctx, const void* source, uint64_t n_source,
+                                                      size_t source_stride_bytes, const void* target, uint64_t n_target,
+                                                      size_t target_stride_bytes, const int32_t* index_query,
+                                                      const int32_t* index_match, uint64_t n, double threshold,
+                                                      const float* transforms, int n_models, uint32_t* out_counts);
+/* The trials the last pclhip_correspondence_rejector_sample_consensus of this context consumed (the first 65,536 at
+ * most): *count always, the first min(capacity, *count) records to buf (host). */
+PCLHIP_API pclhip_status pclhip_rejector_sac_last_trace(pclhip_ctx* ctx, pclhip_rejector_sac_trace* buf, uint64_t capacity,
+                                                        uint64_t* count);
+/* The last PCLHIP_REJ_SAMPLE_CONSENSUS rejector this registration applied: its best transformation (row-major; the
+ * identity without a model) and its statistics.  They synchronise on their own, like pclhip_icp_last_median_distance;
+ * PCLHIP_ERR_STATE when no such rejector has run. */
+PCLHIP_API pclhip_status pclhip_icp_last_sac_transformation(const pclhip_icp* icp, float T[16]);
+PCLHIP_API pclhip_status pclhip_icp_last_sac_stats(const pclhip_icp* icp, pclhip_rejector_sac_stats* out);
+
 /* One iteration on the device-resident working source cloud (a search kernel and a streaming
  * accumulation kernel):
  *   cur <- T_prev * cur   (transformCloud, impl/icp.hpp:49-111 / transforms.hpp:109-123)

@@ -15,7 +15,7 @@
 //                                                   registration/include/pcl/registration/correspondence_estimation.h
 //   pclhip::registration::TransformationEstimation (abstract, four overloads) / ...SVD / ...PointToPlaneLLS /
 //   ...SymmetricPointToPlaneLLS                     registration/include/pcl/registration/transformation_estimation*.h
-//   pclhip::registration::CorrespondenceRejector{Distance,MedianDistance,OneToOne,Trimmed}
+//   pclhip::registration::CorrespondenceRejector{Distance,MedianDistance,OneToOne,Trimmed,SampleConsensus}
 //   pclhip::Registration<S,T> (abstract) / IterativeClosestPoint / IterativeClosestPointWithNormals
 //                                                   registration/include/pcl/registration/registration.h, icp.h
 //   pclhip::NormalEstimation, pclhip::VoxelGrid, pclhip::io::loadPCDFile / savePCDFile*
@@ -803,6 +803,8 @@ class CorrespondenceRejector {
   pclhip_rejector desc{PCLHIP_REJ_DISTANCE, 0.0, 0, 0};
   virtual ~CorrespondenceRejector() = default;
   const std::string& getClassName() const { return rejection_name_; }
+  // after an alignment: what the chain's last application left for this object's getters (SampleConsensus)
+  virtual void readBack(const pclhip_icp*) {}
  protected:
   std::string rejection_name_;
 };
@@ -827,6 +829,129 @@ struct CorrespondenceRejectorTrimmed : CorrespondenceRejector {
   float getOverlapRatio() const { return float(desc.param); }
   void setMinCorrespondences(unsigned n) { desc.min_correspondences = n; }
   unsigned getMinCorrespondences() const { return desc.min_correspondences; }
+};
+
+// pcl::registration::CorrespondenceRejectorSampleConsensus<PointT> (correspondence_rejection_sample_consensus.h,
+// impl/correspondence_rejection_sample_consensus.hpp:55-142; the semantics are stated in include/pclhip.h): standalone through
+// getRemainingCorrespondences / setInputCorrespondences + getCorrespondences, or a member of an ICP's chain
+// (addCorrespondenceRejector), where the inlier threshold, max_iterations and the seed travel in `desc` and
+// getBestTransformation() is filled after the alignment.  setRefineModel(true) is not built: the output stays empty and
+// getLastError() says why.
+template <typename PointT>
+class CorrespondenceRejectorSampleConsensus : public CorrespondenceRejector {
+ public:
+  using Ptr = std::shared_ptr<CorrespondenceRejectorSampleConsensus<PointT>>;
+  using ConstPtr = std::shared_ptr<const CorrespondenceRejectorSampleConsensus<PointT>>;
+  using PointCloudConstPtr = typename PointCloud<PointT>::ConstPtr;
+  CorrespondenceRejectorSampleConsensus() : CorrespondenceRejectorSampleConsensus(Context::defaultContext()) {}
+  explicit CorrespondenceRejectorSampleConsensus(Context::Ptr ctx) : ctx_(std::move(ctx)) {
+    desc.kind = PCLHIP_REJ_SAMPLE_CONSENSUS;
+    desc.param = 0.05;                // inlier_threshold_
+    desc.min_correspondences = 1000;  // max_iterations_
+    desc.reserved = 0;                // the seed of the draws
+    rejection_name_ = "CorrespondenceRejectorSampleConsensus";
+  }
+  void setInputSource(const PointCloudConstPtr& cloud) { input_ = cloud; }
+  PointCloudConstPtr getInputSource() const { return input_; }
+  void setInputTarget(const PointCloudConstPtr& cloud) { target_ = cloud; }
+  PointCloudConstPtr getInputTarget() const { return target_; }
+  bool requiresSourcePoints() const { return true; }
+  bool requiresTargetPoints() const { return true; }
+  void setInlierThreshold(double threshold) { desc.param = threshold; }
+  double getInlierThreshold() const { return desc.param; }
+  void setMaximumIterations(int max_iterations) { desc.min_correspondences = unsigned(std::max(max_iterations, 0)); }  // :177
+  int getMaximumIterations() const { return int(desc.min_correspondences); }
+  void setRefineModel(bool refine) { refine_ = refine; }
+  bool getRefineModel() const { return refine_; }
+  void setSaveInliers(bool s) { save_inliers_ = s; }
+  bool getSaveInliers() const { return save_inliers_; }
+  void setSeed(std::uint32_t seed) { desc.reserved = seed; }
+  std::uint32_t getSeed() const { return desc.reserved; }
+  Matrix4f getBestTransformation() const { return best_transformation_; }
+  void getInliersIndices(Indices& indices) const { indices = inlier_indices_; }
+  const pclhip_rejector_sac_stats& getLastStats() const { return stats_; }
+  const std::string& getLastError() const { return error_; }
+
+  void setInputCorrespondences(const CorrespondencesPtr& correspondences) { input_correspondences_ = correspondences; }
+  void getCorrespondences(Correspondences& correspondences) {
+    correspondences.clear();
+    if (input_correspondences_) getRemainingCorrespondences(*input_correspondences_, correspondences);
+  }
+
+  void getRemainingCorrespondences(const Correspondences& original, Correspondences& remaining) {
+    remaining.clear();
+    error_.clear();
+    if (save_inliers_) inlier_indices_.clear();
+    if (!input_ || !target_ || !ctx_ || !ctx_->ok()) {
+      error_ = rejection_name_ + ": setInputSource and setInputTarget first";
+      return;
+    }
+    Indices q, m;
+    lists(original, q, m);
+    pclhip_rejector_sac_params p = params();
+    Indices pos(original.size());
+    std::uint64_t n_out = 0;
+    const pclhip_status rc = pclhip_correspondence_rejector_sample_consensus(
+        ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), target_->points.data(), target_->size(),
+        sizeof(PointT), q.data(), m.data(), original.size(), &p, pos.data(), pos.size(), &n_out, best_transformation_.m,
+        &stats_);
+    if (rc != PCLHIP_OK) {  // refused (refine, duplicate query indices, an index outside a cloud): an empty solution
+      error_ = pclhip_last_error(ctx_->get());
+      best_transformation_.setIdentity();
+      return;
+    }
+    remaining.reserve(std::size_t(n_out));
+    for (std::uint64_t i = 0; i < n_out; ++i) remaining.push_back(original[std::size_t(pos[std::size_t(i)])]);
+    if (save_inliers_ && stats_.has_model) inlier_indices_.assign(pos.begin(), pos.begin() + std::ptrdiff_t(n_out));
+  }
+
+  // countWithinDistance of row-major 4x4 transforms over a list (exposed for tests)
+  std::vector<std::uint32_t> evaluate(const Correspondences& list, const std::vector<Matrix4f>& transforms) {
+    std::vector<std::uint32_t> counts(transforms.size(), 0u);
+    error_.clear();
+    if (!input_ || !target_ || !ctx_ || !ctx_->ok() || transforms.empty()) return counts;
+    Indices q, m;
+    lists(list, q, m);
+    std::vector<float> T(16 * transforms.size());
+    for (std::size_t i = 0; i < transforms.size(); ++i) std::memcpy(&T[16 * i], transforms[i].m, 16 * sizeof(float));
+    if (pclhip_rejector_sac_evaluate(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT),
+                                     target_->points.data(), target_->size(), sizeof(PointT), q.data(), m.data(), list.size(),
+                                     desc.param, T.data(), int(transforms.size()), counts.data()) != PCLHIP_OK)
+      error_ = pclhip_last_error(ctx_->get());
+    return counts;
+  }
+
+  void readBack(const pclhip_icp* icp) override {
+    if (pclhip_icp_last_sac_transformation(icp, best_transformation_.m) != PCLHIP_OK) best_transformation_.setIdentity();
+    if (pclhip_icp_last_sac_stats(icp, &stats_) != PCLHIP_OK) stats_ = pclhip_rejector_sac_stats();
+  }
+
+ private:
+  static void lists(const Correspondences& c, Indices& q, Indices& m) {
+    q.resize(c.size());
+    m.resize(c.size());
+    for (std::size_t i = 0; i < c.size(); ++i) {
+      q[i] = c[i].index_query;
+      m[i] = c[i].index_match;
+    }
+  }
+  pclhip_rejector_sac_params params() const {
+    pclhip_rejector_sac_params p;
+    pclhip_rejector_sac_params_default(&p);
+    p.inlier_threshold = desc.param;
+    p.max_iterations = int(desc.min_correspondences);
+    p.seed = desc.reserved;
+    p.refine = refine_ ? 1 : 0;
+    return p;
+  }
+  Context::Ptr ctx_;
+  PointCloudConstPtr input_, target_;
+  CorrespondencesPtr input_correspondences_;
+  bool refine_ = false, save_inliers_ = false;
+  Matrix4f best_transformation_;
+  Indices inlier_indices_;
+  pclhip_rejector_sac_stats stats_ = pclhip_rejector_sac_stats();
+  std::string error_;
 };
 
 // pcl::registration::TransformationEstimation (transformation_estimation.h:50-125): the four overloads
@@ -1349,6 +1474,8 @@ class IterativeClosestPoint : public Registration<PointSource, PointTarget> {
       fillParams(p, mode);
       pclhip_icp_result r;
       if (pclhip_icp_align(icp_, &p, guess.m, &r) != PCLHIP_OK) return;
+      if (r.nr_iterations > 0 || r.num_correspondences > 0)
+        for (const auto& rej : this->correspondence_rejectors_) rej->readBack(icp_);
       std::memcpy(this->final_transformation_.m, r.final_transformation, sizeof r.final_transformation);
       std::memcpy(this->transformation_.m, r.last_transformation, sizeof r.last_transformation);
       this->converged_ = r.converged != 0;

@@ -7,7 +7,7 @@ from ._lib import (POINT_TO_PLANE, POINT_TO_POINT, SAC_RANSAC, SACMODEL_NORMAL_P
                    SACMODEL_PARALLEL_PLANE, SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PLANE, SYMMETRIC, PclHipError,
                    PclHipUnavailable)
 from .api import (BoundaryEstimation, Communicator, Context, CorrespondenceEstimation, CorrespondenceRejectorDistance,  # noqa: F401
-                  CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne,
+                  CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne, CorrespondenceRejectorSampleConsensus,
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, MovingLeastSquares, NormalDistributionsTransform, NormalEstimation,

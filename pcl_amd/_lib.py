@@ -138,6 +138,22 @@ class SacModelTrace(C.Structure):
                 ("valid", C.c_int)]
 
 
+class RejectorSacParams(C.Structure):
+    _fields_ = [("inlier_threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
+                ("seed", C.c_uint64), ("batch_size", C.c_int), ("refine", C.c_int)]
+
+
+class RejectorSacStats(C.Structure):
+    _fields_ = [("trials", C.c_uint64), ("iterations", C.c_int), ("best_trial", C.c_int), ("best_count", C.c_uint32),
+                ("remaining", C.c_uint32), ("has_model", C.c_int), ("no_sample", C.c_int), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("sample_dist_thresh", C.c_double)]
+
+
+class RejectorSacTrace(C.Structure):
+    _fields_ = [("samples", C.c_int * 3), ("attempts", C.c_int), ("no_sample", C.c_int), ("transformation", C.c_float * 16),
+                ("count", C.c_uint32)]
+
+
 SACMODEL_PLANE = 0   # sample_consensus/model_types.h:47
 SACMODEL_PERPENDICULAR_PLANE = 9
 SACMODEL_NORMAL_PLANE = 11
@@ -185,7 +201,7 @@ class PcdInfo(C.Structure):
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2
 
-REJ_DISTANCE, REJ_MEDIAN_DISTANCE, REJ_ONE_TO_ONE, REJ_TRIMMED = 0, 1, 2, 3
+REJ_DISTANCE, REJ_MEDIAN_DISTANCE, REJ_ONE_TO_ONE, REJ_TRIMMED, REJ_SAMPLE_CONSENSUS = 0, 1, 2, 3, 4
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
@@ -285,6 +301,15 @@ SIGNATURES = {
     "pclhip_icp_set_rejectors": (C.c_int, [_vp, C.POINTER(Rejector), C.c_int]),
     "pclhip_icp_last_median_distance": (C.c_double, [_vp]),
     "pclhip_icp_set_reciprocal": (C.c_int, [_vp, C.c_int]),
+    "pclhip_rejector_sac_params_default": (None, [C.POINTER(RejectorSacParams)]),
+    "pclhip_correspondence_rejector_sample_consensus": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, _sz, _vp, _vp, _u64,
+                                                                  C.POINTER(RejectorSacParams), _vp, _u64, C.POINTER(_u64),
+                                                                  C.POINTER(C.c_float), C.POINTER(RejectorSacStats)]),
+    "pclhip_rejector_sac_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, _sz, _vp, _vp, _u64, C.c_double,
+                                               C.POINTER(C.c_float), C.c_int, _vp]),
+    "pclhip_rejector_sac_last_trace": (C.c_int, [_vp, C.POINTER(RejectorSacTrace), _u64, C.POINTER(_u64)]),
+    "pclhip_icp_last_sac_transformation": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "pclhip_icp_last_sac_stats": (C.c_int, [_vp, C.POINTER(RejectorSacStats)]),
     "pclhip_icp_iterate": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_double, C.c_int,
                                      C.POINTER(C.c_double)]),
     "pclhip_icp_last_kernel_ms": (C.c_double, [_vp]),

@@ -11,6 +11,7 @@ Class and method names follow the reference so parity tests read like PCL's own 
   pcl::BoundaryEstimation                              features/include/pcl/features/boundary.h
   pcl::VoxelGrid                                       filters/include/pcl/filters/voxel_grid.h:221-533
   pcl::EuclideanClusterExtraction                      segmentation/include/pcl/segmentation/extract_clusters.h:330-435
+  pcl::registration::CorrespondenceRejectorSampleConsensus  registration/.../correspondence_rejection_sample_consensus.h
   pcl::SACSegmentation (planes, RANSAC)                segmentation/include/pcl/segmentation/sac_segmentation.h:77-330
 Clouds are (n, c>=3) float32 arrays: numpy (host) or torch CUDA tensors (device-resident; only the
 pointer crosses the boundary).  All compute happens in libpclhip.so; there is no CPU fallback.
@@ -512,12 +513,191 @@ class CorrespondenceRejectorTrimmed:
         return self.min_corr
 
 
+class CorrespondenceRejectorSampleConsensus:
+    """pcl::registration::CorrespondenceRejectorSampleConsensus<PointT> (correspondence_rejection_sample_consensus.h,
+    impl/correspondence_rejection_sample_consensus.hpp:55-142): RANSAC over the rigid transform of three pairs, the
+    semantics of include/pclhip.h.  Standalone through getRemainingCorrespondences(index_query, index_match), or as a
+    member of a rejector chain (IterativeClosestPoint.addCorrespondenceRejector, CorrespondenceEstimation.
+    determineCorrespondences(rejectors=...)): there param / min_corr / seed travel in the chain's record, and
+    getBestTransformation() / lastStats() are filled from the registration afterwards."""
+    kind = _lib.REJ_SAMPLE_CONSENSUS
+
+    def __init__(self, ctx=None):
+        self._ctx = ctx
+        self.param, self.min_corr, self.seed = 0.05, 1000, 0   # inlier threshold, max_iterations, seed of the draws
+        self._batch = 0
+        self._save_inliers = False
+        self._src = self._tgt = None
+        self._best = np.eye(4, dtype=np.float32)
+        self._inliers = np.zeros(0, np.int32)
+        self._stats = None
+        self._list = (np.zeros(0, np.int32), np.zeros(0, np.int32))
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    def getClassName(self):
+        return "CorrespondenceRejectorSampleConsensus"
+
+    def setInputSource(self, cloud):
+        self._src = cloud
+
+    def getInputSource(self):
+        return self._src
+
+    def setInputTarget(self, cloud):
+        self._tgt = cloud
+
+    def getInputTarget(self):
+        return self._tgt
+
+    def setInlierThreshold(self, threshold):
+        self.param = float(threshold)
+
+    def getInlierThreshold(self):
+        return self.param
+
+    def setMaximumIterations(self, max_iterations):
+        """correspondence_rejection_sample_consensus.h:177: negative values clamp to 0"""
+        self.min_corr = max(int(max_iterations), 0)
+
+    def getMaximumIterations(self):
+        return self.min_corr
+
+    def setRefineModel(self, refine):
+        if refine:
+            raise NotImplementedError("CorrespondenceRejectorSampleConsensus.setRefineModel(True) is not built: refineModel "
+                                      "is a host loop of up to 1,000 data-dependent rounds with a median per round")
+
+    def getRefineModel(self):
+        return False
+
+    def setSaveInliers(self, save):
+        self._save_inliers = bool(save)
+
+    def getSaveInliers(self):
+        return self._save_inliers
+
+    def setSeed(self, seed):
+        """the seed of the draws (32 bits: it travels in pclhip_rejector.reserved when the object sits in a chain)"""
+        self.seed = int(seed) & 0xFFFFFFFF
+
+    def setBatchSize(self, batch):
+        """trials per scoring pass of the standalone call (0: 16 first, then doubling); never changes a result"""
+        self._batch = int(batch)
+
+    def setInputCorrespondences(self, index_query, index_match):
+        """CorrespondenceRejector::setInputCorrespondences: the list evaluate() and getCorrespondences() work on"""
+        self._list = (np.ascontiguousarray(index_query, np.int32).reshape(-1).copy(),
+                      np.ascontiguousarray(index_match, np.int32).reshape(-1).copy())
+
+    def getCorrespondences(self):
+        """CorrespondenceRejector::getCorrespondences: the input list through getRemainingCorrespondences"""
+        return self.getRemainingCorrespondences(*self._list)
+
+    def _lists(self, index_query, index_match):
+        if index_query is None:
+            index_query, index_match = self._list
+        else:
+            self.setInputCorrespondences(index_query, index_match)
+        q = np.ascontiguousarray(index_query, np.int32).reshape(-1)
+        m = np.ascontiguousarray(index_match, np.int32).reshape(-1)
+        if len(q) != len(m):
+            raise ValueError("CorrespondenceRejectorSampleConsensus: index_query and index_match differ in length")
+        assert self._src is not None and self._tgt is not None, "setInputSource / setInputTarget first"
+        return q, m, _cloud(self._src), _cloud(self._tgt)
+
+    def getRemainingCorrespondences(self, index_query, index_match):
+        """-> (index_query, index_match) of the correspondences that remain, in the list's order."""
+        q, m, (sp, ss, sn, sk), (tp, ts, tn, tk) = self._lists(index_query, index_match)
+        lib = self.ctx.lib
+        p = _lib.RejectorSacParams()
+        lib.pclhip_rejector_sac_params_default(C.byref(p))
+        p.inlier_threshold, p.max_iterations, p.seed, p.batch_size = self.param, self.min_corr, self.seed, self._batch
+        pos = np.empty(max(len(q), 1), np.int32)
+        T = np.zeros(16, np.float32)
+        n_out = C.c_uint64(0)
+        st = _lib.RejectorSacStats()
+        check(lib.pclhip_correspondence_rejector_sample_consensus(
+            self.ctx.h, sp, sn, ss, tp, tn, ts, C.c_void_p(q.ctypes.data), C.c_void_p(m.ctypes.data), len(q), C.byref(p),
+            C.c_void_p(pos.ctypes.data), len(q), C.byref(n_out), _fp(T), C.byref(st)), self.ctx.h)
+        pos = pos[:int(n_out.value)].copy()
+        self._fill(T, st)
+        self._inliers = pos if (self._save_inliers and st.has_model) else np.zeros(0, np.int32)
+        return q[pos], m[pos]
+
+    def _fill(self, T, st):
+        self._best = np.array(T, np.float32).reshape(4, 4)
+        self._stats = dict(trials=int(st.trials), iterations=int(st.iterations), best_trial=int(st.best_trial),
+                           best_count=int(st.best_count), remaining=int(st.remaining), has_model=bool(st.has_model),
+                           no_sample=bool(st.no_sample), n=int(st.n), sample_dist_thresh=float(st.sample_dist_thresh))
+
+    def _fill_from_chain(self, lib, ctx, h):
+        T = np.zeros(16, np.float32)
+        st = _lib.RejectorSacStats()
+        if lib.pclhip_icp_last_sac_transformation(h, _fp(T)) == -4:  # PCLHIP_ERR_STATE: the chain has not run (no source point)
+            return
+        check(lib.pclhip_icp_last_sac_transformation(h, _fp(T)), ctx.h)
+        check(lib.pclhip_icp_last_sac_stats(h, C.byref(st)), ctx.h)
+        self._fill(T, st)
+
+    def getBestTransformation(self):
+        """(4, 4) float32: the winner's transformation; the identity when no model was found."""
+        return self._best.copy()
+
+    def getInliersIndices(self):
+        """positions in the input list of the correspondences that remain (setSaveInliers(True); empty without a model)"""
+        return self._inliers.copy()
+
+    def lastStats(self):
+        """dict of the last run: trials, iterations, best_trial, best_count, remaining, has_model, no_sample, n,
+        sample_dist_thresh."""
+        return self._stats
+
+    def evaluate(self, transforms, index_query=None, index_match=None):
+        """countWithinDistance of (H, 4, 4) transforms over the list (given, or the last one this object saw) ->
+        (H,) uint32."""
+        q, m, (sp, ss, sn, sk), (tp, ts, tn, tk) = self._lists(index_query, index_match)
+        M = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
+        cnt = np.zeros(len(M), np.uint32)
+        check(self.ctx.lib.pclhip_rejector_sac_evaluate(
+            self.ctx.h, sp, sn, ss, tp, tn, ts, C.c_void_p(q.ctypes.data), C.c_void_p(m.ctypes.data), len(q),
+            float(self.param), _fp(M), len(M), C.c_void_p(cnt.ctypes.data)), self.ctx.h)
+        return cnt
+
+    def trace(self, capacity=65536):
+        """One dict per trial the last getRemainingCorrespondences() consumed: samples, attempts, no_sample,
+        transformation (4, 4), count."""
+        lib = self.ctx.lib
+        n = C.c_uint64(0)
+        check(lib.pclhip_rejector_sac_last_trace(self.ctx.h, None, 0, C.byref(n)), self.ctx.h)
+        k = min(int(n.value), int(capacity))
+        buf = (_lib.RejectorSacTrace * max(1, k))()
+        check(lib.pclhip_rejector_sac_last_trace(self.ctx.h, buf, k, C.byref(n)), self.ctx.h)
+        return [dict(samples=list(t.samples), attempts=int(t.attempts), no_sample=bool(t.no_sample),
+                     transformation=np.array(t.transformation, np.float32).reshape(4, 4), count=int(t.count))
+                for t in buf[:k]]
+
+
 def _set_filters(lib, ctx, h, rejectors, reciprocal):
     arr = (_lib.Rejector * max(len(rejectors), 1))()
     for i, r in enumerate(rejectors):
         arr[i].kind, arr[i].param, arr[i].min_correspondences = r.kind, r.param, r.min_corr
+        arr[i].reserved = getattr(r, "seed", 0)   # SampleConsensus: the seed of its draws
     check(lib.pclhip_icp_set_rejectors(h, arr, len(rejectors)), ctx.h)
     check(lib.pclhip_icp_set_reciprocal(h, int(bool(reciprocal))), ctx.h)
+
+
+def _read_filters(lib, ctx, h, rejectors):
+    """what the chain's last application left for the rejector objects' getters (each reader synchronises)"""
+    for r in rejectors:
+        if r.kind == _lib.REJ_MEDIAN_DISTANCE:
+            r.median_distance_ = float(lib.pclhip_icp_last_median_distance(h))
+        elif r.kind == _lib.REJ_SAMPLE_CONSENSUS:
+            r._fill_from_chain(lib, ctx, h)
 
 
 class CorrespondenceEstimation:
@@ -582,9 +762,7 @@ class CorrespondenceEstimation:
                 C.byref(cnt)), self.ctx.h)
             c = int(cnt.value)
             assert c == int(sums[28])
-            for r in rejectors:
-                if r.kind == _lib.REJ_MEDIAN_DISTANCE:
-                    r.median_distance_ = float(self.lib.pclhip_icp_last_median_distance(h))
+            _read_filters(self.lib, self.ctx, h, rejectors)
             return q[:c].copy(), m[:c].copy(), d[:c].copy()
         finally:
             self.lib.pclhip_icp_destroy(h)
@@ -903,7 +1081,13 @@ class IterativeClosestPoint:
         md = self.p.max_correspondence_distance if max_dist is None else float(max_dist)
         check(self.lib.pclhip_icp_iterate(self.h, _fp(T.reshape(16)), md, self.MODE,
                                           sums.ctypes.data_as(C.POINTER(C.c_double))), self.ctx.h)
+        self._read_sac_rejectors()
         return sums
+
+    def _read_sac_rejectors(self):
+        sac = [r for r in self.rejectors if r.kind == _lib.REJ_SAMPLE_CONSENSUS]
+        if sac:
+            _read_filters(self.lib, self.ctx, self.h, sac)
 
     def reset(self):
         self._ensure()
@@ -952,6 +1136,8 @@ class IterativeClosestPoint:
         check(self.lib.pclhip_icp_align(self.h, C.byref(self.p), _fp(g) if g is not None else None,
                                         C.byref(r)), self.ctx.h)
         self.result = r
+        if r.nr_iterations > 0 or r.num_correspondences > 0:
+            self._read_sac_rejectors()
         if want_output:
             return self.transformCloud(self.src, self.getFinalTransformation())
         return None

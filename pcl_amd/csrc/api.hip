@@ -449,6 +449,12 @@ pclhip_status pclhip::sharded_filters_ok(pclhip_icp* icp) {
                        "cannot be resolved");
         return PCLHIP_ERR_STATE;
       }
+      // SampleConsensus draws its samples from, and scores its hypotheses on, the ONE list of all kept pairs
+      if (r.kind == PCLHIP_REJ_SAMPLE_CONSENSUS) {
+        set_error(ctx, "the SampleConsensus rejector is not built for multi-GPU iterations: its RANSAC runs over the whole "
+                       "list of correspondences");
+        return PCLHIP_ERR_STATE;
+      }
     }
     if (icp->reciprocal && icp->region.on == 0) {
       set_error(ctx, "reciprocal correspondences need the whole source on every rank: shard the target (pclhip_icp_set_region), "
@@ -1663,6 +1669,7 @@ void pclhip_icp_destroy(pclhip_icp* icp) {
   if (icp->sums_host) pinned_free(icp->ctx, icp->sums_host, PCLHIP_ICP_NSUMS * sizeof(double));
   if (icp->rej_state) (void)dev_free(icp->ctx, icp->rej_state);
   if (icp->rej_state_host) pinned_free(icp->ctx, icp->rej_state_host, sizeof(pclhip::RejState));
+  if (icp->rejsac_host) pinned_free(icp->ctx, icp->rejsac_host, sizeof(pclhip::RejSacState));
   if (icp->ctl) (void)dev_free(icp->ctx, icp->ctl);
   if (icp->ctl_host) pinned_free(icp->ctx, icp->ctl_host, sizeof(pclhip::IcpControl));
   if (icp->steps) pinned_free(icp->ctx, icp->steps, sizeof(pclhip::IcpStepRecord) * size_t(icp->steps_capacity), true);
@@ -1804,7 +1811,12 @@ pclhip_status pclhip_icp_set_allreduce(pclhip_icp* icp, pclhip_allreduce_fn fn, 
 pclhip_status pclhip_icp_set_rejectors(pclhip_icp* icp, const pclhip_rejector* list, int n) {
   if (!icp || n < 0 || (n > 0 && !list)) return PCLHIP_ERR_INVALID;
   for (int i = 0; i < n; ++i)
-    PCLHIP_REQUIRE(icp->ctx, list[i].kind >= PCLHIP_REJ_DISTANCE && list[i].kind <= PCLHIP_REJ_TRIMMED, "unknown rejector kind");
+    PCLHIP_REQUIRE(icp->ctx, list[i].kind >= PCLHIP_REJ_DISTANCE && list[i].kind <= PCLHIP_REJ_SAMPLE_CONSENSUS,
+                   "unknown rejector kind");
+  for (int i = 0; i < n; ++i)  // SampleConsensus: param = inlier threshold, min_correspondences = max_iterations
+    PCLHIP_REQUIRE(icp->ctx, list[i].kind != PCLHIP_REJ_SAMPLE_CONSENSUS ||
+                                 (list[i].param >= 0.0 && list[i].min_correspondences <= 1000000u),
+                   "SampleConsensus rejector: the inlier threshold must be >= 0 and max_iterations at most 1000000");
   icp->rejectors.assign(list, list + n);
   return PCLHIP_OK;
 }

@@ -179,6 +179,28 @@ struct RejState {
   double threshold;        // ... times the factor
 };
 
+// Device-resident state of one CorrespondenceRejectorSampleConsensus run (rejector_sac.hpp): the sample distance threshold,
+// the replay of the RANSAC loop and its result.  One block per application, mirrored to pinned memory for the getters.
+struct RejSacState {
+  double sample_dist_thresh;
+  double log_probability;   // log(1 - probability)
+  double one_over_n;
+  double k;
+  uint32_t n;               // length of the list
+  uint32_t best;            // highest count so far
+  int32_t best_trial;       // -1: none
+  int32_t iterations;
+  uint32_t trials;          // trials consumed
+  uint32_t done;            // the loop has ended: every kernel queued behind it returns at once
+  uint32_t no_sample;       // ... at a trial that found no good sample
+  uint32_t has_model;       // the winner selects at least 3 pairs
+  uint32_t remaining;       // pairs that remain
+  uint32_t bad_index;       // standalone: an index outside its cloud
+  uint32_t duplicate;       // standalone: a query index listed twice
+  uint32_t pad;
+  float T[16];              // the winner's transform while the loop runs, then the best transformation
+};
+
 // The stamps of a step of the marker-free device-driven loop (pclhip_step_clock.hpp: ticks of the constant-rate counter),
 // in a small device block of the registration: the step's kernels leave theirs here, the kernel that closes the step
 // copies the four into the step record and leaves its exit stamp as the next step's start.
@@ -267,6 +289,8 @@ struct pclhip_ctx {
   // the trials the last pclhip_sac_segment_plane consumed (sac.hpp; pclhip_sac_last_trace)
   std::vector<pclhip_sac_plane_trace> sac_trace;
   std::vector<uint8_t> sac_trace_valid;  // the gate's bit of each (sac_models.hpp; pclhip_sac_last_model_trace)
+  // the trials the last pclhip_correspondence_rejector_sample_consensus consumed (rejector_sac.hpp)
+  std::vector<pclhip_rejector_sac_trace> rejsac_trace;
 };
 
 struct pclhip_index {
@@ -365,6 +389,8 @@ struct pclhip_icp {
   bool trim_pending = false;      // a Trimmed rejector ran: fetch_order becomes 2 if rej_state_host->trimmed says it cut
   pclhip::RejState* rej_state = nullptr;       // device
   pclhip::RejState* rej_state_host = nullptr;  // pinned mirror, valid after a stream synchronisation
+  pclhip::RejSacState* rejsac_host = nullptr;  // pinned mirror of the last SampleConsensus rejector's state (rejector_sac.hpp)
+  bool rejsac_ran = false;                     // ... which has been queued at least once
   // device-driven loop (icp_loop.hip)
   pclhip::IcpControl* ctl = nullptr;        // device
   pclhip::IcpControl* ctl_host = nullptr;   // pinned staging copy used to arm the loop

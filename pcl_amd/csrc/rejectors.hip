@@ -2,7 +2,8 @@
 // ICP iteration (registration/include/pcl/registration/impl/icp.hpp:176-201):
 //   * reciprocal correspondences (impl/correspondence_estimation.hpp:220-311)
 //   * the rejector chain: Distance, MedianDistance, OneToOne, Trimmed
-//     (registration/src/correspondence_rejection_{distance,median_distance,one_to_one,trimmed}.cpp)
+//     (registration/src/correspondence_rejection_{distance,median_distance,one_to_one,trimmed}.cpp) and SampleConsensus
+//     (rejector_sac.hpp, which also serves the standalone call at the end of this file)
 // All of them only clear bits of the per-slot `keep` mask; the matches themselves stay in place (they
 // seed the next iteration).  Where the reference leaves the order of exact ties to an unstable
 // std::sort, the lower query index wins.
@@ -14,6 +15,7 @@
 #include <cmath>
 
 #include "pclhip_internal.hpp"
+#include "rejector_sac.hpp"
 
 namespace pclhip {
 namespace {
@@ -515,6 +517,12 @@ pclhip_status apply_correspondence_filters(pclhip_icp* icp, float max_d2, bool u
         trimmed_in_chain = true;  // the list comes back sorted by distance IF it was cut (RejState::trimmed says so)
         break;
       }
+      case PCLHIP_REJ_SAMPLE_CONSENSUS: {
+        // RANSAC over the pairs still kept; the inliers of the winning transform stay (the order of the list is untouched)
+        const pclhip_status sr = rsac_apply_chain(icp, g, r);
+        if (sr != PCLHIP_OK) return sr;
+        break;
+      }
       default:
         set_error(ctx, "unknown rejector kind");
         return PCLHIP_ERR_INVALID;
@@ -563,4 +571,246 @@ void preload_rejector_kernels() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(rs_pick_kernel<0>));
 }
+
+// ---- CorrespondenceRejectorSampleConsensus outside a registration (rejector_sac.hpp) ------------------------------------
+namespace {
+
+// the pairs of a standalone list on the device: pair j in slot j
+struct RsacStaged {
+  float4* S = nullptr;
+  float4* T = nullptr;
+  uint32_t n = 0;
+};
+
+pclhip_status rsac_checked_list(pclhip_ctx* ctx, const void* source, uint64_t n_src, size_t sstride, const void* target,
+                                uint64_t n_tgt, size_t tstride, const int32_t* iq, const int32_t* im, uint64_t n) {
+  PCLHIP_REQUIRE(ctx, sstride >= 12 && sstride % 4 == 0 && tstride >= 12 && tstride % 4 == 0,
+                 "stride must be a multiple of 4 and >= 12 bytes");
+  PCLHIP_REQUIRE(ctx, n_src < 0x7FFFFFFFull && n_tgt < 0x7FFFFFFFull && n < 0x7FFFFFFFull, "cloud too large for int32 indices");
+  PCLHIP_REQUIRE(ctx, (source != nullptr || n_src == 0) && (target != nullptr || n_tgt == 0), "null cloud");
+  PCLHIP_REQUIRE(ctx, n == 0 || (iq != nullptr && im != nullptr), "null correspondence list");
+  PCLHIP_REQUIRE(ctx, n == 0 || (n_src > 0 && n_tgt > 0), "correspondences into an empty cloud");
+  return PCLHIP_OK;
+}
+
+// stage the clouds and the list, gather the pairs, and refuse bad lists (ONE read-back of the state).  st is zero.
+pclhip_status rsac_stage(pclhip_ctx* ctx, DeviceScope& scope, const void* source, uint64_t n_src, size_t sstride,
+                         const void* target, uint64_t n_tgt, size_t tstride, const int32_t* iq, const int32_t* im, uint64_t n,
+                         bool refuse_duplicates, RejSacState* st, RsacStaged* out) {
+  hipStream_t s = ctx->stream;
+  out->n = uint32_t(n);
+  if (n == 0) return PCLHIP_OK;
+  const void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  const void* host[4] = {source, target, iq, im};
+  const size_t bytes[4] = {size_t(n_src) * sstride, size_t(n_tgt) * tstride, size_t(n) * 4, size_t(n) * 4};
+  for (int i = 0; i < 4; ++i) {
+    void* owned = nullptr;
+    const pclhip_status rc = to_device(ctx, host[i], bytes[i], &dev[i], &owned);
+    if (rc != PCLHIP_OK) return rc;
+    if (owned) scope.mem.push_back(owned);
+  }
+  uint32_t* bitmap = nullptr;
+  if (refuse_duplicates) {
+    const size_t words = (size_t(n_src) + 31) / 32;
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&bitmap, words * 4));
+    PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(bitmap, 0, words * 4, s));
+  }
+  PCLHIP_CHECK_HIP(ctx, scope.alloc(&out->S, size_t(n) * sizeof(float4)));
+  PCLHIP_CHECK_HIP(ctx, scope.alloc(&out->T, size_t(n) * sizeof(float4)));
+  hipLaunchKernelGGL(rejsac_gather_kernel, rsac_blocks_of(n), dim3(RSAC_BLOCK), 0, s, static_cast<const char*>(dev[0]), sstride,
+                     n_src, static_cast<const char*>(dev[1]), tstride, n_tgt, static_cast<const int32_t*>(dev[2]),
+                     static_cast<const int32_t*>(dev[3]), uint32_t(n), bitmap, out->S, out->T, st);
+  PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+  RejSacState h;
+  PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+  PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+  PCLHIP_REQUIRE(ctx, h.bad_index == 0u, "a correspondence names a point outside its cloud");
+  PCLHIP_REQUIRE(ctx, h.duplicate == 0u, "a query index is listed twice (the reference would silently keep the last pair)");
+  return PCLHIP_OK;
+}
+
+}  // namespace
 }  // namespace pclhip
+
+extern "C" {
+
+void pclhip_rejector_sac_params_default(pclhip_rejector_sac_params* p) {
+  if (!p) return;
+  // correspondence_rejection_sample_consensus.h: inlier_threshold_ 0.05, max_iterations_ 1000, refine_ false
+  p->inlier_threshold = 0.05;
+  p->max_iterations = 1000;
+  p->probability = 0.99;
+  p->seed = 0;
+  p->batch_size = 0;
+  p->refine = 0;
+}
+
+pclhip_status pclhip_correspondence_rejector_sample_consensus(
+    pclhip_ctx* ctx, const void* source, uint64_t n_src, size_t sstride, const void* target, uint64_t n_tgt, size_t tstride,
+    const int32_t* index_query, const int32_t* index_match, uint64_t n, const pclhip_rejector_sac_params* params,
+    int32_t* out_positions, uint64_t capacity, uint64_t* out_n, float out_T[16], pclhip_rejector_sac_stats* out_stats) {
+  using namespace pclhip;
+  if (!ctx || !params || !out_n) return PCLHIP_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *out_n = 0;
+  ctx->rejsac_trace.clear();
+  PCLHIP_REQUIRE(ctx, params->refine == 0,
+                 "setRefineModel(true) is not built: refineModel is a host loop of data-dependent rounds with a median each");
+  RsacRun R;
+  R.threshold = params->inlier_threshold;
+  R.max_iterations = params->max_iterations;
+  R.probability = params->probability;
+  R.seed = params->seed;
+  R.batch_size = params->batch_size;
+  pclhip_status rc = rsac_checked_run(ctx, R);
+  if (rc != PCLHIP_OK) return rc;
+  if ((rc = rsac_checked_list(ctx, source, n_src, sstride, target, n_tgt, tstride, index_query, index_match, n)) != PCLHIP_OK)
+    return rc;
+  PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DeviceScope scope(ctx);
+  RsacWork w;
+  if ((rc = rsac_alloc_work(ctx, scope, R.max_iterations, &w)) != PCLHIP_OK) return rc;
+  RsacStaged pc;
+  if ((rc = rsac_stage(ctx, scope, source, n_src, sstride, target, n_tgt, tstride, index_query, index_match, n, true, w.st,
+                       &pc)) != PCLHIP_OK)
+    return rc;
+  RsacPairs P;
+  P.src = pc.S;
+  P.tgt = pc.T;
+  P.list = nullptr;
+  P.m_dev = nullptr;
+  P.m_host = pc.n;
+  P.slots = pc.n;
+  RejSacState h;
+  std::memset(&h, 0, sizeof h);
+  if (pc.n == 0) {  // an empty list stays empty: no model
+    for (int e = 0; e < 16; ++e) h.T[e] = kIdentity16[e];
+    h.best_trial = -1;
+  } else {
+    const uint32_t rec_cap = uint32_t(w.trials < RSAC_TRACE_MAX ? w.trials : RSAC_TRACE_MAX);
+    pclhip_rejector_sac_trace* rec = nullptr;
+    uint32_t *flag = nullptr, *excl = nullptr, *tot = nullptr;
+    uint2* partial = nullptr;
+    int32_t* dpos = nullptr;
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&rec, size_t(rec_cap) * sizeof(pclhip_rejector_sac_trace)));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&flag, size_t(pc.n) * 4));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&excl, size_t(pc.n) * 4));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&partial, ((size_t(pc.n) + SC_BLOCK - 1) / SC_BLOCK) * sizeof(uint2)));
+    PCLHIP_CHECK_HIP(ctx, scope.alloc(&tot, 4 * sizeof(uint32_t)));
+    const float bound = rsac_float_bound(R.threshold);
+    if ((rc = rsac_queue_run(ctx, P, R, w, bound, rec, rec_cap)) != PCLHIP_OK) return rc;
+    hipLaunchKernelGGL(rejsac_flag_kernel, rsac_blocks_of(pc.n), dim3(RSAC_BLOCK), 0, s, pc.S, pc.T, pc.n, w.st, bound, flag);
+    launch_scan_u32(s, flag, pc.n, partial, tot, excl);
+    const bool out_dev = out_positions != nullptr && is_device_pointer(out_positions);
+    if (out_positions != nullptr && capacity > 0) {
+      dpos = out_positions;
+      if (!out_dev) PCLHIP_CHECK_HIP(ctx, scope.alloc(&dpos, size_t(capacity < pc.n ? capacity : pc.n) * 4));
+      hipLaunchKernelGGL(rejsac_positions_kernel, rsac_blocks_of(pc.n), dim3(RSAC_BLOCK), 0, s, flag, excl, pc.n, dpos,
+                         capacity < pc.n ? capacity : uint64_t(pc.n));
+    }
+    PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&h, w.st, sizeof h, hipMemcpyDeviceToHost, s));
+    PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    // the trace: the consumed trials' records with their counts
+    const uint64_t kept = h.trials < rec_cap ? h.trials : rec_cap;
+    if (kept > 0) {
+      std::vector<uint32_t> counts(kept);
+      ctx->rejsac_trace.resize(kept);
+      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->rejsac_trace.data(), rec, size_t(kept) * sizeof(pclhip_rejector_sac_trace),
+                                           hipMemcpyDeviceToHost, s));
+      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(counts.data(), w.counts, size_t(kept) * 4, hipMemcpyDeviceToHost, s));
+      PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+      for (uint64_t t = 0; t < kept; ++t) ctx->rejsac_trace[t].count = ctx->rejsac_trace[t].no_sample ? 0u : counts[t];
+    }
+    if (dpos != nullptr && !out_dev && h.remaining > 0 && h.remaining <= capacity) {
+      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(out_positions, dpos, size_t(h.remaining) * 4, hipMemcpyDeviceToHost, s));
+      PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    }
+  }
+  *out_n = h.remaining;
+  if (out_T) std::memcpy(out_T, h.T, 16 * sizeof(float));
+  if (out_stats) rsac_stats_of(h, out_stats);
+  if (out_positions != nullptr && h.remaining > capacity) {
+    set_error(ctx, "SampleConsensus rejector: output capacity too small (out_n holds the required number)");
+    return PCLHIP_ERR_OVERFLOW;
+  }
+  return PCLHIP_OK;
+}
+
+pclhip_status pclhip_rejector_sac_evaluate(pclhip_ctx* ctx, const void* source, uint64_t n_src, size_t sstride,
+                                           const void* target, uint64_t n_tgt, size_t tstride, const int32_t* index_query,
+                                           const int32_t* index_match, uint64_t n, double threshold, const float* transforms,
+                                           int n_models, uint32_t* out_counts) {
+  using namespace pclhip;
+  if (!ctx || n_models < 0 || (n_models > 0 && (!transforms || !out_counts))) return PCLHIP_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  pclhip_status rc = rsac_checked_list(ctx, source, n_src, sstride, target, n_tgt, tstride, index_query, index_match, n);
+  if (rc != PCLHIP_OK) return rc;
+  PCLHIP_REQUIRE(ctx, threshold >= 0.0, "SampleConsensus rejector: the inlier threshold must be >= 0");
+  PCLHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DeviceScope scope(ctx);
+  RejSacState* st = nullptr;
+  PCLHIP_CHECK_HIP(ctx, scope.alloc(&st, sizeof(RejSacState)));
+  PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(st, 0, sizeof(RejSacState), s));
+  RsacStaged pc;
+  if ((rc = rsac_stage(ctx, scope, source, n_src, sstride, target, n_tgt, tstride, index_query, index_match, n, false, st,
+                       &pc)) != PCLHIP_OK)
+    return rc;
+  for (int m = 0; m < n_models; ++m) out_counts[m] = 0u;
+  if (pc.n == 0 || n_models == 0) return PCLHIP_OK;
+  float* Ts = nullptr;
+  uint32_t* counts = nullptr;
+  PCLHIP_CHECK_HIP(ctx, scope.alloc(&Ts, size_t(RSAC_MAX_BATCH) * 12 * sizeof(float)));
+  PCLHIP_CHECK_HIP(ctx, scope.alloc(&counts, size_t(RSAC_MAX_BATCH) * 4));
+  const float bound = rsac_float_bound(threshold);
+  const uint32_t grid = rsac_count_grid(ctx, pc.n);
+  std::vector<float> rows(size_t(RSAC_MAX_BATCH) * 12);
+  for (int m0 = 0; m0 < n_models; m0 += RSAC_MAX_BATCH) {
+    const uint32_t H = uint32_t(n_models - m0 < RSAC_MAX_BATCH ? n_models - m0 : RSAC_MAX_BATCH);
+    for (uint32_t h = 0; h < H; ++h) std::memcpy(&rows[size_t(h) * 12], transforms + size_t(m0 + h) * 16, 12 * sizeof(float));
+    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(Ts, rows.data(), size_t(H) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(counts, 0, size_t(H) * 4, s));
+    hipLaunchKernelGGL(rejsac_count_kernel, dim3(grid), dim3(RSAC_BLOCK), 0, s, pc.S, pc.T, pc.n,
+                       reinterpret_cast<const float4*>(Ts), H, bound, static_cast<const RejSacState*>(nullptr), counts);
+    PCLHIP_CHECK_HIP(ctx, hipGetLastError());
+    PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(out_counts + m0, counts, size_t(H) * 4, hipMemcpyDeviceToHost, s));
+    PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+  }
+  return PCLHIP_OK;
+}
+
+pclhip_status pclhip_rejector_sac_last_trace(pclhip_ctx* ctx, pclhip_rejector_sac_trace* buf, uint64_t capacity,
+                                             uint64_t* count) {
+  if (!ctx || !count || (capacity > 0 && !buf)) return PCLHIP_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mutex);
+  *count = ctx->rejsac_trace.size();
+  const uint64_t m = capacity < *count ? capacity : *count;
+  if (m > 0) std::memcpy(buf, ctx->rejsac_trace.data(), size_t(m) * sizeof(pclhip_rejector_sac_trace));
+  return PCLHIP_OK;
+}
+
+pclhip_status pclhip_icp_last_sac_transformation(const pclhip_icp* icp, float T[16]) {
+  if (!icp || !T) return PCLHIP_ERR_INVALID;
+  if (!icp->rejsac_ran || !icp->rejsac_host) {
+    pclhip::set_error(icp->ctx, "no SampleConsensus rejector has run in this registration");
+    return PCLHIP_ERR_STATE;
+  }
+  (void)hipStreamSynchronize(icp->ctx->stream);  // the chain mirrors its state to pinned memory stream-ordered
+  std::memcpy(T, icp->rejsac_host->T, 16 * sizeof(float));
+  return PCLHIP_OK;
+}
+
+pclhip_status pclhip_icp_last_sac_stats(const pclhip_icp* icp, pclhip_rejector_sac_stats* out) {
+  if (!icp || !out) return PCLHIP_ERR_INVALID;
+  if (!icp->rejsac_ran || !icp->rejsac_host) {
+    pclhip::set_error(icp->ctx, "no SampleConsensus rejector has run in this registration");
+    return PCLHIP_ERR_STATE;
+  }
+  (void)hipStreamSynchronize(icp->ctx->stream);
+  pclhip::rsac_stats_of(*icp->rejsac_host, out);
+  return PCLHIP_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,8 @@
 //   slots 0 .. nr_samples-1               the sample draws of selectSamples (draw j picks from n_src - j)
 //   slots nr_samples .. 2 nr_samples-1    the pick among the k nearest features of sample j
 // The result therefore does not depend on how iterations are batched, and a test can replay every draw.
+// CorrespondenceRejectorSampleConsensus (rejector_sac.hpp) keys its draws by (seed, trial, attempt, slot): draw_index_attempt
+// below; tests/rejector_sac_restatement.py restates it.
 #pragma once
 
 #include <stdint.h>
@@ -18,11 +20,24 @@ namespace scp {
 
 constexpr int MAX_SAMPLES = 8;  // nr_samples of an alignment (the trace record holds that many)
 
-PCLHIP_HD uint64_t draw_bits(uint64_t seed, uint32_t iteration, uint32_t slot) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (((uint64_t(iteration) << 8) | uint64_t(slot)) + 1ull);
+PCLHIP_HD uint64_t draw_mix(uint64_t seed, uint64_t counter) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (counter + 1ull);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+
+PCLHIP_HD uint64_t draw_bits(uint64_t seed, uint32_t iteration, uint32_t slot) {
+  return draw_mix(seed, (uint64_t(iteration) << 8) | uint64_t(slot));
+}
+
+// CorrespondenceRejectorSampleConsensus redraws a bad sample INSIDE its trial (SampleConsensusModel::getSamples, sac_model.h:
+// 162-197, up to 1,000 attempts): there a draw is a pure function of (seed, trial, attempt, slot), the same finalizer over
+// the counter (trial << 24) | (attempt << 8) | slot (attempt < 65536, slot < 256).
+PCLHIP_HD int draw_index_attempt(uint64_t seed, uint32_t trial, uint32_t attempt, uint32_t slot, int n) {
+  const uint64_t x = draw_mix(seed, (uint64_t(trial) << 24) | (uint64_t(attempt) << 8) | uint64_t(slot));
+  const double u = double(x >> 11) * (1.0 / 9007199254740992.0);
+  return int(double(n) * u);
 }
 
 // getRandomIndex(n): an index in [0, n)

@@ -1,0 +1,255 @@
+"""numpy restatement of pcl::registration::CorrespondenceRejectorSampleConsensus (registration/include/pcl/registration/impl/
+correspondence_rejection_sample_consensus.hpp:55-142, sample_consensus/.../impl/sac_model_registration.hpp:48-97,203-249,
+289-322, sac_model_registration.h:264-289, sac_model.h:162-197, impl/ransac.hpp:56-217) with the project's draws
+(pcl_amd/csrc/scp_draw.hpp: draw_index_attempt), as include/pclhip.h states it.
+
+Per pair everything is elementwise float32 numpy, which does not contract a multiply with an add: the bit pattern the device
+has to meet.  umeyama is float64 (numpy's SVD, tests/scp_restatement.py), rounded once to float32.  The covariance is summed
+in float64 and rounded once to float32; its eigenvalues follow pcl::eigen33 / computeRoots in float32.  The stopping rule is
+float64 with libm's log and pow."""
+import math
+import sys
+
+import numpy as np
+
+import scp_restatement as sr
+
+F = np.float32
+DBL_EPS = sys.float_info.epsilon
+DBL_MAX = sys.float_info.max
+M64 = (1 << 64) - 1
+MAX_SAMPLE_CHECKS = 1000
+
+
+# ---- draws ------------------------------------------------------------------------------------------------------------------
+def draw_index_attempt(seed, trial, attempt, slot, n):
+    """scp_draw.hpp: the splitmix finalizer over the counter (trial << 24) | (attempt << 8) | slot, u = (x >> 11) * 2^-53,
+    int(n * u)"""
+    counter = (trial << 24) | (attempt << 8) | slot
+    z = (seed + 0x9E3779B97F4A7C15 * (counter + 1)) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    z ^= z >> 31
+    return int(float(n) * (float(z >> 11) * (1.0 / 9007199254740992.0)))
+
+
+def draw_samples(seed, trial, attempt, n):
+    """three distinct list positions, ascending: draw j picks from n - j, placed by insert_samples"""
+    return sr.insert_samples([draw_index_attempt(seed, trial, attempt, j, n - j) for j in range(3)])
+
+
+# ---- sample distance threshold -------------------------------------------------------------------------------------------------
+def compute_roots2(b, c):
+    b, c = F(b), F(c)
+    d = F(np.float64(F(b * b)) - 4.0 * np.float64(c))
+    if d < 0:
+        d = F(0)
+    sd = F(np.sqrt(d))
+    return [F(0), F(F(0.5) * F(b - sd)), F(F(0.5) * F(b + sd))]
+
+
+def compute_roots(m):
+    """common/include/pcl/common/impl/eigen.hpp:68-128 in float32, operation by operation (normals_math.hpp)"""
+    m = np.asarray(m, F)
+    with np.errstate(all="ignore"):
+        c0 = (F(F(m[0, 0] * m[1, 1]) * m[2, 2]) + F(F(F(F(2) * m[0, 1]) * m[0, 2]) * m[1, 2]) -
+              F(F(m[0, 0] * m[1, 2]) * m[1, 2]) - F(F(m[1, 1] * m[0, 2]) * m[0, 2]) - F(F(m[2, 2] * m[0, 1]) * m[0, 1]))
+        c1 = (F(m[0, 0] * m[1, 1]) - F(m[0, 1] * m[0, 1]) + F(m[0, 0] * m[2, 2]) - F(m[0, 2] * m[0, 2]) +
+              F(m[1, 1] * m[2, 2]) - F(m[1, 2] * m[1, 2]))
+        c2 = F(F(m[0, 0] + m[1, 1]) + m[2, 2])
+        c0, c1 = F(c0), F(c1)
+        if abs(c0) < np.finfo(F).eps:
+            return compute_roots2(c2, c1)
+        s_inv3, s_sqrt3 = F(1.0 / 3.0), F(np.sqrt(F(3)))
+        c2_over_3 = F(c2 * s_inv3)
+        a_over_3 = F(F(c1 - F(c2 * c2_over_3)) * s_inv3)
+        if a_over_3 > 0:
+            a_over_3 = F(0)
+        half_b = F(F(0.5) * F(c0 + F(c2_over_3 * F(F(F(F(2) * c2_over_3) * c2_over_3) - c1))))
+        q = F(F(half_b * half_b) + F(F(a_over_3 * a_over_3) * a_over_3))
+        if q > 0:
+            q = F(0)
+        rho = F(np.sqrt(F(-a_over_3)))
+        theta = F(F(np.arctan2(F(np.sqrt(F(-q))), half_b)) * s_inv3)
+        cos_theta, sin_theta = F(np.cos(theta)), F(np.sin(theta))
+        r = [F(c2_over_3 + F(F(F(2) * rho) * cos_theta)),
+             F(c2_over_3 - F(rho * F(cos_theta + F(s_sqrt3 * sin_theta)))),
+             F(c2_over_3 - F(rho * F(cos_theta - F(s_sqrt3 * sin_theta))))]
+        if r[0] >= r[1]:
+            r[0], r[1] = r[1], r[0]
+        if r[1] >= r[2]:
+            r[1], r[2] = r[2], r[1]
+            if r[0] >= r[1]:
+                r[0], r[1] = r[1], r[0]
+        if r[0] <= 0:
+            return compute_roots2(c2, c1)
+        return r
+
+
+def sample_dist_thresh(src_pts):
+    """computeSampleDistanceThreshold (sac_model_registration.h:264-289) over the list's source points -> float64 (NaN for
+    a negative eigenvalue); 0.0 when no point is finite"""
+    p = np.asarray(src_pts, F)
+    if len(p) == 0:
+        return 0.0
+    ok = np.isfinite(p).all(axis=1)
+    if not ok.any():
+        return 0.0
+    K = p[0].astype(np.float64) if ok[0] else np.zeros(3)
+    d = p[ok].astype(np.float64) - K
+    cnt = float(len(d))
+    a = np.array([(d[:, 0] * d[:, 0]).sum(), (d[:, 0] * d[:, 1]).sum(), (d[:, 0] * d[:, 2]).sum(), (d[:, 1] * d[:, 1]).sum(),
+                  (d[:, 1] * d[:, 2]).sum(), (d[:, 2] * d[:, 2]).sum(), d[:, 0].sum(), d[:, 1].sum(), d[:, 2].sum()]) / cnt
+    cov = np.zeros((3, 3), F)
+    cov[0, 0], cov[0, 1], cov[0, 2] = a[0] - a[6] * a[6], a[1] - a[6] * a[7], a[2] - a[6] * a[8]
+    cov[1, 1], cov[1, 2], cov[2, 2] = a[3] - a[7] * a[7], a[4] - a[7] * a[8], a[5] - a[8] * a[8]
+    cov[1, 0], cov[2, 0], cov[2, 1] = cov[0, 1], cov[0, 2], cov[1, 2]
+    scale = F(np.abs(cov).max())
+    if scale <= np.finfo(F).tiny:
+        scale = F(1)
+    ev = compute_roots((cov / scale).astype(F))
+    with np.errstate(all="ignore"):
+        r = [F(np.sqrt(F(e * scale))) for e in ev]
+        s = F(F(r[0] + r[1]) + r[2])
+    d = float(s) / 3.0
+    return d * d
+
+
+def is_sample_good(p0, p1, p2, thresh):
+    """isSampleGood (:48-66): the three float32 squared edge lengths, each as a double above the threshold"""
+    with np.errstate(all="ignore"):
+        return bool(float(sr.edge_sq(p0, p1)) > thresh and float(sr.edge_sq(p0, p2)) > thresh and
+                    float(sr.edge_sq(p1, p2)) > thresh)
+
+
+def get_samples(src_pts, seed, trial, thresh):
+    """getSamples (sac_model.h:162-197) -> (samples of the last attempt, attempts made, found)"""
+    n = len(src_pts)
+    s = [0, 0, 0]
+    for attempt in range(MAX_SAMPLE_CHECKS):
+        s = draw_samples(seed, trial, attempt, n)
+        if is_sample_good(src_pts[s[0]], src_pts[s[1]], src_pts[s[2]], thresh):
+            return s, attempt + 1, True
+    return s, MAX_SAMPLE_CHECKS, False
+
+
+# ---- hypothesis and score ------------------------------------------------------------------------------------------------------
+def hypothesis(src3, tgt3):
+    """pcl::umeyama(src, tgt, false) in float64 -> (T float32 (4, 4), T64)"""
+    with np.errstate(all="ignore"):
+        T64 = sr.umeyama(np.asarray(src3, F), np.asarray(tgt3, F))
+    return T64.astype(F), T64
+
+
+def pair_d2(T, src_pts, tgt_pts):
+    """p = ((Tr0 s.x + Tr1 s.y) + Tr2 s.z) + Tr3, e = p - t, d2 = (e.x e.x + e.z e.z) + e.y e.y in float32"""
+    T = np.asarray(T, F)
+    s, t = np.asarray(src_pts, F), np.asarray(tgt_pts, F)
+    with np.errstate(all="ignore"):
+        e = [(((T[r, 0] * s[:, 0] + T[r, 1] * s[:, 1]) + T[r, 2] * s[:, 2]) + T[r, 3]) - t[:, r] for r in range(3)]
+        return (e[0] * e[0] + e[2] * e[2]) + e[1] * e[1]
+
+
+def within(T, src_pts, tgt_pts, threshold):
+    """inlier iff double(d2) < threshold * threshold (a double product); never for a non-finite pair"""
+    with np.errstate(all="ignore"):
+        return pair_d2(T, src_pts, tgt_pts).astype(np.float64) < float(threshold) * float(threshold)
+
+
+def count_within(T, src_pts, tgt_pts, threshold):
+    return int(np.count_nonzero(within(T, src_pts, tgt_pts, threshold)))
+
+
+# ---- the loop --------------------------------------------------------------------------------------------------------------------
+class Replay:
+    """ransac.hpp:154-201 on a sequence of counts: sac_replay.hpp's rule without its skip branch"""
+
+    def __init__(self, max_iterations, probability, n):
+        self.max_iterations = int(max_iterations)
+        self.log_probability = math.log(1.0 - probability)
+        self.one_over_n = 1.0 / float(n)
+        self.iterations = 0
+        self.best = 0
+        self.k = DBL_MAX
+        self.best_trial = -1
+        self.trials = 0
+        self.done = False
+
+    def feed(self, count):
+        trial = self.trials
+        self.trials += 1
+        if count > self.best:
+            self.best = int(count)
+            self.best_trial = trial
+            w = float(self.best) * self.one_over_n
+            p = 1.0 - math.pow(w, 3.0)
+            p = max(DBL_EPS, p)
+            p = min(1.0 - DBL_EPS, p)
+            self.k = self.log_probability / math.log(p)
+        self.iterations += 1
+        if self.iterations > self.k or self.iterations > self.max_iterations:
+            self.done = True
+            return False
+        return True
+
+
+def reject(src_cloud, tgt_cloud, index_query, index_match, threshold=0.05, max_iterations=1000, probability=0.99, seed=0,
+           transforms=None):
+    """getRemainingCorrespondences -> dict(remaining (list positions), index_query, index_match, T (best transformation),
+    has_model, no_sample, iterations, trials, best_trial, best_count, sample_dist_thresh, k_margin (the smallest
+    |iterations - k| / k the stopping rule met), trace [dict(samples, attempts, no_sample, T, T64, count)]).
+    transforms: {trial: (4, 4) float32} replaces the restatement's own umeyama (the device's, for a parity test)."""
+    q = np.asarray(index_query, np.int64).reshape(-1)
+    m = np.asarray(index_match, np.int64).reshape(-1)
+    n = len(q)
+    s = np.asarray(src_cloud, F)[:, :3][q]
+    t = np.asarray(tgt_cloud, F)[:, :3][m]
+    thresh = sample_dist_thresh(s)
+    out = dict(has_model=False, no_sample=False, iterations=0, trials=0, best_trial=-1, best_count=0,
+               sample_dist_thresh=thresh, trace=[], k_margin=math.inf)
+    best_T = None
+    if n >= 3:
+        r = Replay(max_iterations, probability, n)
+        while not r.done:
+            trial = r.trials
+            smp, attempts, found = get_samples(s, int(seed), trial, thresh)
+            if not found:  # "No samples could be selected" (ransac.hpp:120-124)
+                out["trace"].append(dict(samples=smp, attempts=attempts, no_sample=True, T=np.zeros((4, 4), F), T64=None,
+                                         count=0))
+                r.trials += 1
+                out["no_sample"] = True
+                break
+            T, T64 = hypothesis(s[smp], t[smp])
+            if transforms is not None:
+                T = np.asarray(transforms[trial], F)
+            count = count_within(T, s, t, threshold)
+            out["trace"].append(dict(samples=smp, attempts=attempts, no_sample=False, T=T, T64=T64, count=count))
+            before = r.best
+            r.feed(count)
+            if r.best != before:
+                best_T = T
+            if r.k < DBL_MAX:
+                out["k_margin"] = min(out["k_margin"], abs(r.iterations - r.k) / r.k)
+        out.update(iterations=r.iterations, trials=r.trials, best_trial=r.best_trial, best_count=r.best)
+    if best_T is not None and out["best_count"] >= 3:
+        keep = np.nonzero(within(best_T, s, t, threshold))[0]
+        out.update(has_model=True, T=np.asarray(best_T, F).copy())
+    else:
+        keep = np.arange(n)
+        out["T"] = np.eye(4, dtype=F)
+    out.update(remaining=keep.astype(np.int32), index_query=q[keep].astype(np.int32), index_match=m[keep].astype(np.int32))
+    return out
+
+
+def threshold_margin(trace, src_pts, tgt_pts, threshold):
+    """the smallest |d2 - threshold^2| / threshold^2 over every pair under every scored T of a trace"""
+    t2 = float(threshold) * float(threshold)
+    worst = math.inf
+    for rec in trace:
+        if rec["no_sample"]:
+            continue
+        d2 = pair_d2(rec["T"], src_pts, tgt_pts).astype(np.float64)
+        d2 = d2[np.isfinite(d2)]
+        if len(d2):
+            worst = min(worst, float(np.abs(d2 - t2).min()) / t2)
+    return worst
