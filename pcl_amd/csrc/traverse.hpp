@@ -324,19 +324,22 @@ struct NN1 {
 
 // 1-NN fast path: the hot loop only tracks the minimum DISTANCE (packed v_pk_* math on candidate
 // pairs, one v_min3 per pair) and the LEAF that first reached it (a wave-uniform id: one select).
-// WHICH slot of that leaf won is resolved once per query after the traversal (resolve()): the lane
-// re-reads its winning leaf and recomputes the same 16 distances.  Exact distance ties (two slots of
-// a leaf, or an equal minimum in another leaf) raise `tie`; the caller then re-runs the exact policy
-// NN1 for those lanes, so results stay bit-identical to the oracle.
+// The minimum is kept per HALF of the block (slots 0-7, slots 8-15: two accumulators instead of one, the same
+// v_min3 per pair), so the winning half comes with it for one compare.
+// WHICH slot of that half won is resolved once per query after the traversal (resolve()): the lane
+// re-reads the half -- six 16-byte loads -- and recomputes the same 8 distances.  Exact distance ties (two
+// slots of a leaf -- in one half: resolve() sees both; one in each half: the half minima are equal -- or an equal
+// minimum in another leaf) raise `tie`; the caller then re-runs the exact policy NN1 for those lanes, so results stay
+// bit-identical to the oracle.
 template <int Q>
 struct NN1MinT {
   static constexpr int QPL = Q;  // queries per lane: the wave owns 64*Q queries and every staged
                                  // candidate block / node scan / leaf test is shared by all of them
   float best[Q];         // candidates must be strictly below this to win
-  uint32_t bestpos[Q];   // sorted position of the winner; while `unres`: first slot of the winning leaf;
-                         // NO_INDEX while best is only the bound
+  uint32_t bestpos[Q];   // sorted position of the winner; while `unres`: first slot of the winning half of the
+                         // winning leaf; NO_INDEX while best is only the bound
   bool tie[Q];
-  bool unres[Q];         // the winner's slot inside leaf bestpos/LEAF is not known yet
+  bool unres[Q];         // the winner's slot inside that half is not known yet
   __device__ __forceinline__ void init(float bound_exclusive) {
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
@@ -346,6 +349,8 @@ struct NN1MinT {
       unres[q] = false;
     }
   }
+  // Only while nothing is unresolved -- before the traversal, or behind resolve() (standoff.hpp seeds its lanes there): an
+  // unresolved bestpos is the first slot of a half, which resolve() relies on, and a seed's position is any slot.
   __device__ __forceinline__ void seed(int q, float d, uint32_t pos) {
     if (d < best[q]) {
       best[q] = d;
@@ -355,11 +360,11 @@ struct NN1MinT {
   __device__ __forceinline__ float worst(int q) const { return best[q]; }
   __device__ __forceinline__ void leaf(const float* l, uint32_t leaf_id, const float* qx, const float* qy,
                                        const float* qz) {
-    float m[Q];
+    float mh[Q][2];  // the minimum of slots 0-7 and of slots 8-15
     v2f qx2[Q], qy2[Q], qz2[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      m[q] = __builtin_inff();
+      mh[q][0] = mh[q][1] = __builtin_inff();
       qx2[q] = v2f{qx[q], qx[q]};
       qy2[q] = v2f{qy[q], qy[q]};
       qz2[q] = v2f{qz[q], qz[q]};
@@ -369,24 +374,27 @@ struct NN1MinT {
 #pragma unroll
       for (int q = 0; q < Q; ++q) {  // one broadcast read of the pair serves all Q queries
         const v2f r = pair_dist(l, j, qx2[q], qy2[q], qz2[q]);
-        m[q] = __builtin_fminf(m[q], __builtin_fminf(r.x, r.y));
+        mh[q][j / (LEAF / 4)] = __builtin_fminf(mh[q][j / (LEAF / 4)], __builtin_fminf(r.x, r.y));
       }
     }
-    const uint32_t first = leaf_id * LEAF;
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const bool imp = m[q] < best[q];
-      // equal minimum in another leaf than the current winner's: index tie, the exact policy decides;
-      // equal minimum in the winner's own leaf (a seed re-found -- or another slot at exactly the seed's
-      // distance): resolve() looks at the slots
-      const bool eq = (m[q] == best[q]) && (bestpos[q] != NO_INDEX);
-      const bool same = bestpos[q] / LEAF == leaf_id;
-      tie[q] = imp ? false : (tie[q] || (eq && !same));
-      const bool look = imp || (eq && same);
-      best[q] = imp ? m[q] : best[q];
-      bestpos[q] = look ? first : bestpos[q];
-      unres[q] = unres[q] || look;
-    }
+    for (int q = 0; q < Q; ++q) take(q, mh[q][0], mh[q][1], leaf_id);
+  }
+  // the two half minima of leaf `leaf_id` against query q's best
+  __device__ __forceinline__ void take(int q, float mlo, float mhi, uint32_t leaf_id) {
+    const float m = __builtin_fminf(mlo, mhi);
+    const bool imp = m < best[q];
+    // equal minimum in another leaf than the current winner's: index tie, the exact policy decides;
+    // equal minimum in the winner's own leaf (a seed re-found -- or another slot at exactly the seed's
+    // distance): resolve() looks at the slots of the half that holds it -- and if BOTH halves hold it, two slots tie
+    const bool eq = (m == best[q]) && (bestpos[q] != NO_INDEX);
+    const bool same = bestpos[q] / LEAF == leaf_id;
+    const bool both = mlo == mhi;
+    tie[q] = imp ? both : (tie[q] || (eq && (!same || both)));
+    const bool look = imp || (eq && same);
+    best[q] = imp ? m : best[q];
+    bestpos[q] = look ? (leaf_id * LEAF) | (mhi < mlo ? uint32_t(LEAF / 2) : 0u) : bestpos[q];
+    unres[q] = unres[q] || look;
   }
   // Lane-sparse evaluation (traverse(): SPARSE): every lane evaluates ITS OWN leaf (id NO_INDEX = none),
   // staged in batch slot `slot` of the transposed LDS buffer -- a lane only pays for the leaves its own
@@ -409,9 +417,10 @@ struct NN1MinT {
                                           const float* qz) {
     if (leaf_id != NO_INDEX) {
       const v2f qx2 = {qx[0], qx[0]}, qy2 = {qy[0], qy[0]}, qz2 = {qz[0], qz[0]};
-      float m = __builtin_inff();
+      float mh[2] = {__builtin_inff(), __builtin_inff()};  // the minimum of chunks 0-1 and of chunks 2-3
 #pragma unroll
       for (int c4 = 0; c4 < LEAF / 4; ++c4) {
+        float& m = mh[c4 / 2];
         // (quad_dist written out, here and in resolve(): through the helper the schedule of the ICP search kernels moves)
         const float4 X = s[c4 * STRIDE], Y = s[(LEAF / 4 + c4) * STRIDE], Z = s[(2 * (LEAF / 4) + c4) * STRIDE];
         {
@@ -429,17 +438,10 @@ struct NN1MinT {
           m = __builtin_fminf(m, __builtin_fminf(r.x, r.y));
         }
       }
-      const bool imp = m < best[0];
-      const bool eq = (m == best[0]) && (bestpos[0] != NO_INDEX);  // see leaf()
-      const bool same = bestpos[0] / LEAF == leaf_id;
-      tie[0] = imp ? false : (tie[0] || (eq && !same));
-      const bool look = imp || (eq && same);
-      best[0] = imp ? m : best[0];
-      bestpos[0] = look ? leaf_id * LEAF : bestpos[0];
-      unres[0] = unres[0] || look;
+      take(0, mh[0], mh[1], leaf_id);
     }
   }
-  // after the traversal: find the winning slot inside the winning leaf (same arithmetic, same bits)
+  // after the traversal: find the winning slot inside the winning half of the winning leaf (same arithmetic, same bits)
   __device__ __forceinline__ void resolve(const IndexView& ix, const float* qx, const float* qy, const float* qz) {
     resolve(ix.soa, qx, qy, qz);
   }
@@ -448,12 +450,14 @@ struct NN1MinT {
     for (int q = 0; q < Q; ++q) {
       if (__builtin_amdgcn_ballot_w64(unres[q]) == 0) continue;
       if (unres[q]) {
-        const float4* s = reinterpret_cast<const float4*>(soa + size_t(bestpos[q] / LEAF) * LEAF_FLOATS);
+        // chunks 0-1 or 2-3 of x, y and z: bestpos is the first slot of the half
+        const float4* s = reinterpret_cast<const float4*>(soa + size_t(bestpos[q] / LEAF) * LEAF_FLOATS) +
+                          (bestpos[q] % LEAF) / 4;
         uint32_t hit = 0;
-        // the 16 distances on packed v_pk_* math, exactly as the evaluation computed them (scalar: +0.7 % per converged iteration)
+        // the 8 distances on packed v_pk_* math, exactly as the evaluation computed them (scalar: +0.7 % per converged iteration)
         const v2f qx2 = {qx[q], qx[q]}, qy2 = {qy[q], qy[q]}, qz2 = {qz[q], qz[q]};
 #pragma unroll
-        for (int c4 = 0; c4 < LEAF / 4; ++c4) {
+        for (int c4 = 0; c4 < LEAF / 8; ++c4) {
           const float4 X = s[c4], Y = s[LEAF / 4 + c4], Z = s[2 * (LEAF / 4) + c4];
           {
             const v2f dx = qx2 - v2f{X.x, X.y}, dy = qy2 - v2f{Y.x, Y.y}, dz = qz2 - v2f{Z.x, Z.y};
@@ -474,7 +478,7 @@ struct NN1MinT {
         }
         // hit == 0 cannot happen (identical operations); if it ever did, the exact policy takes over
         tie[q] = tie[q] || hit == 0u || (hit & (hit - 1u)) != 0u;
-        bestpos[q] = hit ? (bestpos[q] / LEAF) * LEAF + uint32_t(__builtin_ctz(hit)) : NO_INDEX;
+        bestpos[q] = hit ? bestpos[q] + uint32_t(__builtin_ctz(hit)) : NO_INDEX;
         unres[q] = false;
       }
     }
