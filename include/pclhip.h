@@ -1294,6 +1294,125 @@ PCLHIP_API pclhip_status pclhip_sac_model_evaluate(pclhip_ctx* ctx, const void* 
 PCLHIP_API pclhip_status pclhip_sac_last_model_trace(pclhip_ctx* ctx, pclhip_sac_model_trace* buf, uint64_t capacity,
                                                      uint64_t* count);
 
+/* ---- SampleConsensusModelCylinder under RandomSampleConsensus --------------------------------------------
+ * pcl::SampleConsensusModelCylinder<PointT, PointNT> (sample_consensus/.../impl/sac_model_cylinder.hpp:49-140,182-265,
+ * 268-309,453-489, sample_consensus/src/sac_model_cylinder.cpp:42-143, common/.../distances.h:75-80, common/impl/common.hpp:
+ * 58-68) run by pcl::RandomSampleConsensus (impl/ransac.hpp:56-217), and one call, pclhip_sac_cylinder_segment, that does
+ * with them what SACSegmentation::segment does (segmentation/.../impl/sac_segmentation.hpp:79-133).  The segmentation
+ * classes themselves still refuse model type 5 (SACMODEL_CYLINDER): the cylinder lives at the level of the model and the
+ * RANSAC objects.  Coefficients: (line_pt x y z, line_dir x y z, radius).  The point set, the draws, the replay, the lists
+ * and the outputs are those of pclhip_sac_segment_plane, with a sample of TWO: trial t draws scp::select_samples(seed, t,
+ * 2, n), s0 < s1, and the stopping rule's exponent is 2.  Normals: one record (nx, ny, nz, curvature) per record of the
+ * cloud, as for the normal plane; the curvature is not read.
+ * Two orders of a float sum of three products, no contraction anywhere:
+ *   dot3(u, v)  = (u.x v.x + u.z v.z) + u.y v.y     a Vector4f with w = 0 (the plane models' order, above)
+ *   dot3v(u, v) = u.x v.x + (u.y v.y + u.z v.z)     an Eigen::Vector3f: Eigen's unrolled scalar reduction of size 3 splits
+ *                                                   1 + 2 (stated from Eigen's redux_novec_unroller)
+ * normalized3v(v) = v / sqrtf(dot3v(v, v)) when that is > 0, else v.  angle(rad) = acos(clamp(double(rad), -1, 1)) folded
+ * with min(a, M_PI - a), as above.
+ * The model of a sample (computeModelCoefficients, :75-140), p1, p2 the points at s0, s1 and n1, n2 their RAW normal
+ * records, all as Vector4f with w = 0:
+ *   w = (n1 + p1) - p2, line_dir = n1 x n2, b = dot3(n1, n2), c = dot3(n2, n2), d = dot3(n1, w), e = dot3(n2, w),
+ *   denominator = dot3(line_dir, line_dir), sc = double(denominator) < 1e-8 ? 0 : (b e - c d) / denominator,
+ *   line_pt = (p1 + n1) + sc n1, line_dir /= sqrtf(denominator) when denominator > 0,
+ *   radius = float(0.5 * (sqrt(double(q1)) + sqrt(double(q2)))), q = dot3(x, x) / dot3(line_dir, line_dir) in float with
+ *   x = line_dir x (line_pt - p).
+ * The trial is SKIPPED (no iteration; the call ends at 10 * max_iterations skips) when fabsf(p1 - p2) <= FLT_EPSILON in
+ * every coordinate or when double(radius) > radius_max or < radius_min (the defaults -+DBL_MAX never fire).  A non-finite
+ * point or normal in the sample is not a skip: its trial counts 0.
+ * The gate (isModelValid, :453-489): with eps_angle > 0 invalid when angle(dot3v(normalized3v(axis),
+ * normalized3v(line_dir))) > eps_angle; invalid when radius_min is set (!= -DBL_MAX) and double(radius) < radius_min, or
+ * radius_max is set and double(radius) > radius_max.  An invalid hypothesis is an iteration that counts 0, not a skip.
+ * The distance of a point p with unit normal n (the normal plane's: normalized((nx, ny, nz)) in dot3's order), against
+ * (line_pt, l = normalized3v(line_dir), radius), :206-221:
+ *   diff = p - line_pt, dir = diff - dot3v(diff, l) l, e = fabsf(sqrtf(dot3v(dir, dir)) - radius)        (float)
+ *   wed = (1.0 - normal_distance_weight) * double(e);  wed > threshold: not an inlier
+ *   d_normal = angle(dot3v(n, normalized3v(dir)))
+ *   inlier iff fabs(normal_distance_weight * d_normal + wed) < threshold                                  (double)
+ * in counting and both selections: one function.  The weight is the plain normal_distance_weight (no curvature, :170).  A
+ * zero dir or normal stays zero (dot 0, angle pi/2); a NaN anywhere is never an inlier.  The scoring pass replaces the
+ * test on wed, for 0 <= normal_distance_weight <= 1, by e >= e_out with e_out the least float that fails it (the product
+ * is monotone in e, so the two agree on every float); its flags are those of the function above.
+ * getDistancesToModel: fabs(normal_distance_weight * d_normal + wed) for every point, without the exit; none for an
+ * invalid model.
+ * The refit (optimizeModelCoefficients, :268-309; src/sac_model_cylinder.cpp:42-143) runs when the coefficients pass the
+ * gate and there are more than 2 inliers.  The frame: ref_dir the unit axis, ref_pt the axis point nearest the inliers'
+ * centroid, u the unit vector among x / z / y picked by |ref_dir.x| < |ref_dir.y| ? (|ref_dir.x| < |ref_dir.z| ? x : z) : y
+ * made orthogonal to ref_dir, v = ref_dir x u.  Unknowns (a, b, c, d, r) from (0, 0, 0, 0, radius); residual of inlier i:
+ *   f_i = |(ref_pt + a u + b v - p_i) x normalized(ref_dir + c u + d v)| - |r|
+ * minimised by Levenberg-Marquardt on the device in double: the sums of f^2, J^T f and J^T J over the inliers in a fixed
+ * order, then a damped (H + lambda diag H) 5x5 Cholesky step, accepted when the sum of squares falls.  It stops when every
+ * |g_a| <= 1e-12 sqrt(H_aa sum f^2), when a step is below 1e-12 of the unknowns' scales (|r| for a, b, r; 1 for c, d), or
+ * after 100 steps.  Outputs: line_pt, the direction rounded to float and then normalized3v, |r|.  A non-finite value, a
+ * Cholesky that fails at the largest damping, or no accepted step keep the unrefined coefficients (refined 0).  After the
+ * refit the gate runs again: a refined cylinder that fails it gives an EMPTY inlier list and keeps the refined
+ * coefficients.  Two calls give the same bytes.
+ * Refused (PCLHIP_ERR_INVALID with a message): no normals, or a normals stride below 16 bytes; a zero axis with eps_angle
+ * > 0; radius_min > radius_max; what pclhip_sac_segment_plane refuses.
+ * Deviations, beyond the plane's: the reference minimises with Eigen's MINPACK port in float (ftol = xtol =
+ * sqrt(FLT_EPSILON)), this converges past float resolution; the frame and the centroid are double; at most 100 steps
+ * against 400 function evaluations; the point normals are normalised in dot3's order (the normal plane's staging); the
+ * double acos and sqrt are the device's.  Not built: refineModel, setNumberOfThreads, projectPoints, doSamplesVerifyModel,
+ * setSamplesMaxDist. */
+typedef struct {
+  double normal_distance_weight;    /* default 0.1 */
+  double radius_min;                /* default -DBL_MAX: not set */
+  double radius_max;                /* default DBL_MAX: not set */
+  float axis[3];                    /* default 0, 0, 0 */
+  double eps_angle;                 /* radians; <= 0 (default 0): no angle gate */
+} pclhip_sac_cylinder_params;
+typedef struct {                    /* one entry per consumed trial (pclhip_sac_last_cylinder_trace) */
+  int samples[2];                   /* ascending positions in the point set */
+  int skipped;
+  float coefficients[7];            /* as computed */
+  uint32_t count;                   /* 0 for a skipped and for an invalid trial */
+  int valid;                        /* 0: skipped, or the hypothesis failed the gate */
+} pclhip_sac_cylinder_trace;
+PCLHIP_API void pclhip_sac_cylinder_params_default(pclhip_sac_cylinder_params* p);
+/* RandomSampleConsensus::computeModel, then with params->optimize_coefficients the refit and the second selection. */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_segment(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                     const void* normals, size_t normals_stride_bytes,
+                                                     const int32_t* indices, uint64_t n_indices,
+                                                     const pclhip_sac_plane_params* params,
+                                                     const pclhip_sac_cylinder_params* model, float out_coeff[7],
+                                                     int32_t* out_inliers, uint64_t inliers_capacity, uint64_t* out_n_inliers,
+                                                     int32_t* out_outliers, uint64_t outliers_capacity,
+                                                     uint64_t* out_n_outliers, pclhip_sac_plane_stats* out_stats);
+/* computeModelCoefficients of samples[0], samples[1] (cloud indices, in this order): *out_found 0 where the reference
+ * returns false (out_coeff then holds what was computed). */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_model(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                   const void* normals, size_t normals_stride_bytes,
+                                                   const int32_t samples[2], const pclhip_sac_cylinder_params* model,
+                                                   float out_coeff[7], int* out_found);
+/* countWithinDistance and isModelValid of n_models septuples (host): out_counts[m] (host; 0 for an invalid one),
+ * out_valid[m] (host, optional). */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_evaluate(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                      const void* normals, size_t normals_stride_bytes,
+                                                      const int32_t* indices, uint64_t n_indices, double threshold,
+                                                      const pclhip_sac_cylinder_params* model, const float* coeffs,
+                                                      int n_models, uint32_t* out_counts, uint8_t* out_valid);
+/* selectWithinDistance: cloud indices in the order of the point set (host or device; null: the count alone). */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_select(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                    const void* normals, size_t normals_stride_bytes,
+                                                    const int32_t* indices, uint64_t n_indices, double threshold,
+                                                    const pclhip_sac_cylinder_params* model, const float coeff[7],
+                                                    int32_t* out_inliers, uint64_t inliers_capacity, uint64_t* out_n_inliers);
+/* getDistancesToModel: one double per entry of the point set (host or device); *out_n 0 for an invalid model. */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_distances(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                       const void* normals, size_t normals_stride_bytes,
+                                                       const int32_t* indices, uint64_t n_indices,
+                                                       const pclhip_sac_cylinder_params* model, const float coeff[7],
+                                                       double* out_distances, uint64_t capacity, uint64_t* out_n);
+/* optimizeModelCoefficients over `inliers` (cloud indices): out_coeff = coeff where nothing was refined; *out_refined,
+ * *out_iterations (the Levenberg-Marquardt steps tried), both optional. */
+PCLHIP_API pclhip_status pclhip_sac_cylinder_optimize(pclhip_ctx* ctx, const void* cloud, uint64_t n, size_t stride_bytes,
+                                                      const int32_t* inliers, uint64_t n_inliers,
+                                                      const pclhip_sac_cylinder_params* model, const float coeff[7],
+                                                      float out_coeff[7], int* out_refined, int* out_iterations);
+/* The trials the last pclhip_sac_cylinder_segment of this context consumed (the first 65,536 at most). */
+PCLHIP_API pclhip_status pclhip_sac_last_cylinder_trace(pclhip_ctx* ctx, pclhip_sac_cylinder_trace* buf, uint64_t capacity,
+                                                        uint64_t* count);
+
 /* ---- VoxelGrid ----------------------------------------------------------------------------------
  * Replaces pcl::VoxelGrid<pcl::PointXYZ>::applyFilter (filters/include/pcl/filters/impl/
  * voxel_grid.hpp:597-814) with downsample_all_data and the optional pass-through filter in front of

@@ -2775,4 +2775,239 @@ class SACSegmentationFromNormals : public SACSegmentation<PointT> {
   PointCloudNConstPtr normals_;
 };
 
+// ---- pcl::SampleConsensusModelCylinder<PointT, PointNT> (sample_consensus/include/pcl/sample_consensus/
+// sac_model_cylinder.h, impl/sac_model_cylinder.hpp) and pcl::RandomSampleConsensus<PointT> (ransac.h, impl/ransac.hpp:
+// 56-217) over the pclhip_sac_cylinder_* calls; include/pclhip.h states the semantics.  SACSegmentation above still refuses
+// SACMODEL_CYLINDER: the cylinder lives at this level.  Not built: refineModel, setNumberOfThreads, projectPoints,
+// doSamplesVerifyModel, setSamplesMaxDist.
+// What the model interface uses of Eigen::VectorXf: a resizable array of floats.
+struct VectorXf {
+  std::vector<float> v;
+  VectorXf() = default;
+  explicit VectorXf(std::size_t n) : v(n, 0.0f) {}
+  std::size_t size() const { return v.size(); }
+  void resize(std::size_t n) { v.resize(n); }
+  float& operator[](std::size_t i) { return v[i]; }
+  float operator[](std::size_t i) const { return v[i]; }
+  const float* data() const { return v.data(); }
+  float* data() { return v.data(); }
+};
+
+// what RandomSampleConsensus needs of a model: the one call that scores, replays and selects
+template <typename PointT>
+class SampleConsensusModel {
+ public:
+  using Ptr = std::shared_ptr<SampleConsensusModel<PointT>>;
+  virtual ~SampleConsensusModel() = default;
+  virtual unsigned int getSampleSize() const = 0;
+  virtual unsigned int getModelSize() const = 0;
+  const std::string& getLastError() const { return error_; }
+  // computeModel (optimize false) or what SACSegmentation::segment does; false: refused (getLastError) or no model
+  virtual bool runRansac(const pclhip_sac_plane_params& params, bool optimize, Indices& sample, Indices& inliers,
+                         Indices& outliers, VectorXf& coefficients, pclhip_sac_plane_stats& stats) = 0;
+
+ protected:
+  std::string error_;
+};
+
+template <typename PointT, typename PointNT>
+class SampleConsensusModelCylinder : public SampleConsensusModel<PointT> {
+ public:
+  using Ptr = std::shared_ptr<SampleConsensusModelCylinder<PointT, PointNT>>;
+  using PointCloudConstPtr = typename PointCloud<PointT>::ConstPtr;
+  using PointCloudNConstPtr = typename PointCloud<PointNT>::ConstPtr;
+  explicit SampleConsensusModelCylinder(const PointCloudConstPtr& cloud, bool = false)
+      : SampleConsensusModelCylinder(cloud, Context::defaultContext()) {}
+  SampleConsensusModelCylinder(const PointCloudConstPtr& cloud, Context::Ptr ctx) : ctx_(std::move(ctx)), input_(cloud) {
+    pclhip_sac_cylinder_params_default(&model_);
+  }
+  SampleConsensusModelCylinder(const PointCloudConstPtr& cloud, const Indices& indices, bool = false)
+      : SampleConsensusModelCylinder(cloud, indices, Context::defaultContext()) {}
+  SampleConsensusModelCylinder(const PointCloudConstPtr& cloud, const Indices& indices, Context::Ptr ctx)
+      : SampleConsensusModelCylinder(cloud, std::move(ctx)) {
+    setIndices(indices);
+  }
+  void setInputCloud(const PointCloudConstPtr& cloud) { input_ = cloud; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setIndices(const Indices& indices) { indices_ = indices; subset_ = true; }
+  void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setNormalDistanceWeight(double w) { model_.normal_distance_weight = w; }
+  double getNormalDistanceWeight() const { return model_.normal_distance_weight; }
+  void setRadiusLimits(const double& min_radius, const double& max_radius) { model_.radius_min = min_radius; model_.radius_max = max_radius; }
+  void getRadiusLimits(double& min_radius, double& max_radius) const { min_radius = model_.radius_min; max_radius = model_.radius_max; }
+  void setAxis(const Vector3f& ax) { for (int i = 0; i < 3; ++i) model_.axis[i] = ax[i]; }
+  Vector3f getAxis() const { return Vector3f(model_.axis[0], model_.axis[1], model_.axis[2]); }
+  void setEpsAngle(double ea) { model_.eps_angle = ea; }
+  double getEpsAngle() const { return model_.eps_angle; }
+  unsigned int getSampleSize() const override { return 2; }
+  unsigned int getModelSize() const override { return 7; }
+
+  bool computeModelCoefficients(const Indices& samples, VectorXf& model_coefficients) {
+    if (samples.size() != 2 || !stage()) return false;
+    float c[7];
+    int found = 0;
+    if (!ok(pclhip_sac_cylinder_model(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), records_.data(), 16,
+                                      samples.data(), &model_, c, &found)) || !found)
+      return false;
+    model_coefficients.v.assign(c, c + 7);
+    return true;
+  }
+  std::size_t countWithinDistance(const VectorXf& model_coefficients, double threshold) {
+    if (model_coefficients.size() != 7 || !stage()) return 0;
+    std::uint32_t count = 0;
+    if (!ok(pclhip_sac_cylinder_evaluate(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), records_.data(), 16,
+                                         ip(), ni(), threshold, &model_, model_coefficients.data(), 1, &count, nullptr)))
+      return 0;
+    return count;
+  }
+  void selectWithinDistance(const VectorXf& model_coefficients, double threshold, Indices& inliers) {
+    inliers.clear();
+    if (model_coefficients.size() != 7 || !stage()) return;
+    const std::size_t m = subset_ ? indices_.size() : input_->size();
+    Indices in(m > 0 ? m : 1);
+    std::uint64_t n_in = 0;
+    if (!ok(pclhip_sac_cylinder_select(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), records_.data(), 16, ip(),
+                                       ni(), threshold, &model_, model_coefficients.data(), in.data(), m, &n_in)))
+      return;
+    in.resize(std::size_t(n_in));
+    inliers.swap(in);
+  }
+  void getDistancesToModel(const VectorXf& model_coefficients, std::vector<double>& distances) {
+    distances.clear();
+    if (model_coefficients.size() != 7 || !stage()) return;
+    const std::size_t m = subset_ ? indices_.size() : input_->size();
+    std::vector<double> d(m > 0 ? m : 1);
+    std::uint64_t n_d = 0;
+    if (!ok(pclhip_sac_cylinder_distances(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), records_.data(), 16,
+                                          ip(), ni(), &model_, model_coefficients.data(), d.data(), m, &n_d)))
+      return;
+    d.resize(std::size_t(n_d));
+    distances.swap(d);
+  }
+  void optimizeModelCoefficients(const Indices& inliers, const VectorXf& model_coefficients, VectorXf& optimized_coefficients) {
+    optimized_coefficients = model_coefficients;
+    this->error_.clear();
+    if (model_coefficients.size() != 7 || !input_ || !ctx_ || !ctx_->ok()) return;
+    float c[7];
+    if (!ok(pclhip_sac_cylinder_optimize(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), inliers.data(),
+                                         inliers.size(), &model_, model_coefficients.data(), c, &refined_, &lm_iterations_)))
+      return;
+    optimized_coefficients.v.assign(c, c + 7);
+  }
+  // of the last optimizeModelCoefficients: whether it replaced the coefficients, and the Levenberg-Marquardt steps it tried
+  bool lastRefined() const { return refined_ != 0; }
+  int lastIterations() const { return lm_iterations_; }
+
+  bool runRansac(const pclhip_sac_plane_params& params, bool optimize, Indices& sample, Indices& inliers, Indices& outliers,
+                 VectorXf& coefficients, pclhip_sac_plane_stats& stats) override {
+    sample.clear(); inliers.clear(); outliers.clear(); coefficients.v.clear();
+    stats = pclhip_sac_plane_stats();
+    stats.best_trial = -1;
+    if (!stage()) return false;
+    const std::size_t m = subset_ ? indices_.size() : input_->size();
+    Indices in(m > 0 ? m : 1), out(m > 0 ? m : 1);
+    pclhip_sac_plane_params p = params;
+    p.optimize_coefficients = optimize ? 1 : 0;
+    float c[7];
+    std::uint64_t n_in = 0, n_out = 0;
+    if (!ok(pclhip_sac_cylinder_segment(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), records_.data(), 16,
+                                        ip(), ni(), &p, &model_, c, in.data(), m, &n_in, out.data(), m, &n_out, &stats)))
+      return false;
+    out.resize(std::size_t(n_out));
+    outliers.swap(out);
+    if (stats.best_trial < 0) return false;
+    in.resize(std::size_t(n_in));
+    inliers.swap(in);
+    coefficients.v.assign(c, c + 7);
+    std::vector<pclhip_sac_cylinder_trace> tr(std::size_t(stats.best_trial) + 1);
+    std::uint64_t count = 0;
+    if (ok(pclhip_sac_last_cylinder_trace(ctx_->get(), tr.data(), tr.size(), &count)) && count > std::uint64_t(stats.best_trial)) {
+      for (int k = 0; k < 2; ++k) {
+        const int pos = tr[std::size_t(stats.best_trial)].samples[k];
+        sample.push_back(subset_ ? indices_[std::size_t(pos)] : index_t(pos));
+      }
+    }
+    return true;
+  }
+
+ private:
+  bool ok(pclhip_status rc) {
+    if (rc != PCLHIP_OK) this->error_ = pclhip_last_error(ctx_->get());
+    return rc == PCLHIP_OK;
+  }
+  const index_t* ip() const { return subset_ ? (indices_.empty() ? &none_ : indices_.data()) : nullptr; }
+  std::uint64_t ni() const { return subset_ ? indices_.size() : 0; }
+  // the normals as contiguous (nx, ny, nz, curvature) records; false: refuse the call (error_ says why)
+  bool stage() {
+    this->error_.clear();
+    if (!input_ || !ctx_ || !ctx_->ok()) {
+      this->error_ = "SampleConsensusModelCylinder: no input cloud or no device";
+      return false;
+    }
+    if (!normals_ || normals_->size() != input_->size()) {  // impl/sac_model_cylinder.hpp:85-89
+      this->error_ = "SampleConsensusModelCylinder: setInputNormals with one normal per point first";
+      return false;
+    }
+    const std::size_t n = input_->size();
+    records_.resize(4 * (n > 0 ? n : 1));
+    for (std::size_t i = 0; i < n; ++i) {
+      const PointNT& p = (*normals_)[i];
+      records_[4 * i] = p.normal_x; records_[4 * i + 1] = p.normal_y; records_[4 * i + 2] = p.normal_z;
+      records_[4 * i + 3] = p.curvature;
+    }
+    return true;
+  }
+
+  Context::Ptr ctx_;
+  PointCloudConstPtr input_;
+  PointCloudNConstPtr normals_;
+  Indices indices_;
+  bool subset_ = false;
+  index_t none_ = 0;
+  pclhip_sac_cylinder_params model_;
+  std::vector<float> records_;
+  int refined_ = 0, lm_iterations_ = 0;
+};
+
+template <typename PointT>
+class RandomSampleConsensus {
+ public:
+  using SampleConsensusModelPtr = typename SampleConsensusModel<PointT>::Ptr;
+  explicit RandomSampleConsensus(const SampleConsensusModelPtr& model) : RandomSampleConsensus(model, std::numeric_limits<double>::max()) {}
+  RandomSampleConsensus(const SampleConsensusModelPtr& model, double threshold) : model_(model) {
+    pclhip_sac_plane_params_default(&params_);
+    params_.distance_threshold = threshold;
+    params_.max_iterations = 10000;  // ransac.h:90,101
+    params_.optimize_coefficients = 0;
+  }
+  void setDistanceThreshold(double threshold) { params_.distance_threshold = threshold; }
+  double getDistanceThreshold() const { return params_.distance_threshold; }
+  void setMaxIterations(int max_iterations) { params_.max_iterations = max_iterations; }
+  int getMaxIterations() const { return params_.max_iterations; }
+  void setProbability(double probability) { params_.probability = probability; }
+  double getProbability() const { return params_.probability; }
+  // the draws are a pure function of (seed, trial, slot): include/pclhip.h
+  void setSeed(std::uint64_t seed) { params_.seed = seed; }
+  void setBatchSize(int n) { params_.batch_size = n; }
+  bool computeModel(int = 0) { return model_ && model_->runRansac(params_, false, sample_, inliers_, outliers_, coeff_, stats_); }
+  // what SACSegmentation::segment does with this model and method in one call (impl/sac_segmentation.hpp:79-133)
+  bool segment(bool optimize_coefficients = true) {
+    return model_ && model_->runRansac(params_, optimize_coefficients, sample_, inliers_, outliers_, coeff_, stats_);
+  }
+  void getModel(Indices& model) const { model = sample_; }
+  void getInliers(Indices& inliers) const { inliers = inliers_; }
+  void getOutliers(Indices& outliers) const { outliers = outliers_; }
+  void getModelCoefficients(VectorXf& model_coefficients) const { model_coefficients = coeff_; }
+  const pclhip_sac_plane_stats& getLastStats() const { return stats_; }
+  SampleConsensusModelPtr getSampleConsensusModel() const { return model_; }
+
+ private:
+  SampleConsensusModelPtr model_;
+  pclhip_sac_plane_params params_;
+  pclhip_sac_plane_stats stats_ = pclhip_sac_plane_stats();
+  Indices sample_, inliers_, outliers_;
+  VectorXf coeff_;
+};
+
 }  // namespace pclhip

@@ -11,6 +11,7 @@ from .api import (BoundaryEstimation, Communicator, Context, CorrespondenceEstim
                   CorrespondenceRejectorTrimmed, DefaultConvergenceCriteria, EuclideanClusterExtraction, FPFHEstimation, GeneralizedIterativeClosestPoint,
                   ISSKeypoint3D, IterativeClosestPoint,
                   IterativeClosestPointWithNormals, KdTree, MovingLeastSquares, NormalDistributionsTransform, NormalEstimation,
-                  RadiusOutlierRemoval, RegionGrowing, SACSegmentation, SACSegmentationFromNormals, SampleConsensusPrerejective,
+                  RadiusOutlierRemoval, RandomSampleConsensus, RegionGrowing, SACSegmentation, SACSegmentationFromNormals,
+                  SampleConsensusModelCylinder, SampleConsensusPrerejective,
                   StatisticalOutlierRemoval, VoxelGrid,
                   default_context, estimateRigidTransformation, featureKSearch, getPCDHeader, loadPCDField, loadPCDFile, savePCDFile)

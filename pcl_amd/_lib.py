@@ -138,6 +138,16 @@ class SacModelTrace(C.Structure):
                 ("valid", C.c_int)]
 
 
+class SacCylinderParams(C.Structure):
+    _fields_ = [("normal_distance_weight", C.c_double), ("radius_min", C.c_double), ("radius_max", C.c_double),
+                ("axis", C.c_float * 3), ("eps_angle", C.c_double)]
+
+
+class SacCylinderTrace(C.Structure):
+    _fields_ = [("samples", C.c_int * 2), ("skipped", C.c_int), ("coefficients", C.c_float * 7), ("count", C.c_uint32),
+                ("valid", C.c_int)]
+
+
 class RejectorSacParams(C.Structure):
     _fields_ = [("inlier_threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
                 ("seed", C.c_uint64), ("batch_size", C.c_int), ("refine", C.c_int)]
@@ -289,6 +299,22 @@ SIGNATURES = {
     "pclhip_sac_model_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.c_double, C.POINTER(SacModelParams),
                                             C.POINTER(C.c_float), C.c_int, _vp, _vp]),
     "pclhip_sac_last_model_trace": (C.c_int, [_vp, C.POINTER(SacModelTrace), _u64, C.POINTER(_u64)]),
+    "pclhip_sac_cylinder_params_default": (None, [C.POINTER(SacCylinderParams)]),
+    "pclhip_sac_cylinder_segment": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.POINTER(SacPlaneParams),
+                                              C.POINTER(SacCylinderParams), C.POINTER(C.c_float), _vp, _u64, C.POINTER(_u64),
+                                              _vp, _u64, C.POINTER(_u64), C.POINTER(SacPlaneStats)]),
+    "pclhip_sac_cylinder_model": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, C.POINTER(C.c_int32), C.POINTER(SacCylinderParams),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "pclhip_sac_cylinder_evaluate": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.c_double,
+                                               C.POINTER(SacCylinderParams), C.POINTER(C.c_float), C.c_int, _vp, _vp]),
+    "pclhip_sac_cylinder_select": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.c_double,
+                                             C.POINTER(SacCylinderParams), C.POINTER(C.c_float), _vp, _u64, C.POINTER(_u64)]),
+    "pclhip_sac_cylinder_distances": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _sz, _vp, _u64, C.POINTER(SacCylinderParams),
+                                                C.POINTER(C.c_float), _vp, _u64, C.POINTER(_u64)]),
+    "pclhip_sac_cylinder_optimize": (C.c_int, [_vp, _vp, _u64, _sz, _vp, _u64, C.POINTER(SacCylinderParams),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int)]),
+    "pclhip_sac_last_cylinder_trace": (C.c_int, [_vp, C.POINTER(SacCylinderTrace), _u64, C.POINTER(_u64)]),
     "pclhip_icp_params_default": (None, [C.POINTER(IcpParams)]),
     "pclhip_icp_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pclhip_icp_destroy": (None, [_vp]),

@@ -3178,6 +3178,319 @@ class SACSegmentationFromNormals(SACSegmentation):
         return super()._normal_records(n)
 
 
+def _index_list(indices):
+    """-> (pointer, count, keepalive) of an int32 list, numpy or torch; an empty list still has a pointer"""
+    if _is_torch(indices):
+        import torch
+        idx = indices.to(torch.int32).contiguous()
+        if idx.numel() > 0:
+            return C.c_void_p(idx.data_ptr()), int(idx.numel()), idx
+        indices = np.zeros(0, np.int32)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+    n = len(idx)
+    if n == 0:
+        idx = np.zeros(1, np.int32)
+    return C.c_void_p(idx.ctypes.data), n, idx
+
+
+class SampleConsensusModelCylinder:
+    """pcl::SampleConsensusModelCylinder<PointT, PointNT> (sample_consensus/include/pcl/sample_consensus/
+    sac_model_cylinder.h, impl/sac_model_cylinder.hpp) over the pclhip_sac_cylinder_* calls (include/pclhip.h states the
+    semantics).  The cloud is (n, c >= 3) float32, the normals (n, >= 4) float32 records (nx, ny, nz, curvature), numpy or
+    torch CUDA tensors; `indices` is the point set (None: every record).  Coefficients: (line_pt, line_dir, radius), 7 floats.
+    The segmentation classes still refuse SACMODEL_CYLINDER: run this model with RandomSampleConsensus.  Not built:
+    projectPoints, doSamplesVerifyModel, setSamplesMaxDist."""
+
+    def __init__(self, cloud, indices=None, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.m = _lib.SacCylinderParams()
+        self.lib.pclhip_sac_cylinder_params_default(C.byref(self.m))
+        self._cloud = cloud
+        self._indices = indices
+        self._normals = None
+
+    def setInputCloud(self, cloud):
+        self._cloud = cloud
+
+    def getInputCloud(self):
+        return self._cloud
+
+    def setIndices(self, indices):
+        self._indices = indices
+
+    def getIndices(self):
+        return self._indices
+
+    def setInputNormals(self, normals):
+        self._normals = normals
+
+    def getInputNormals(self):
+        return self._normals
+
+    def setNormalDistanceWeight(self, weight):
+        self.m.normal_distance_weight = float(weight)
+
+    def getNormalDistanceWeight(self):
+        return float(self.m.normal_distance_weight)
+
+    def setRadiusLimits(self, min_radius, max_radius):
+        self.m.radius_min, self.m.radius_max = float(min_radius), float(max_radius)
+
+    def getRadiusLimits(self):
+        return float(self.m.radius_min), float(self.m.radius_max)
+
+    def setAxis(self, axis):
+        a = np.asarray(axis, np.float32).reshape(3)
+        self.m.axis[0], self.m.axis[1], self.m.axis[2] = float(a[0]), float(a[1]), float(a[2])
+
+    def getAxis(self):
+        return np.array(self.m.axis, np.float32)
+
+    def setEpsAngle(self, eps_angle):
+        self.m.eps_angle = float(eps_angle)
+
+    def getEpsAngle(self):
+        return float(self.m.eps_angle)
+
+    def getSampleSize(self):
+        return 2
+
+    def getModelSize(self):
+        return 7
+
+    def _inputs(self):
+        """-> (cloud ptr, n, stride, normals ptr, normals stride, indices ptr, indices count, keepalive)"""
+        assert self._cloud is not None, "the model has no cloud"
+        ptr, stride, n, keep = _cloud(self._cloud)
+        if self._normals is None:  # impl/sac_model_cylinder.hpp:85-89
+            raise ValueError("SampleConsensusModelCylinder: setInputNormals first")
+        nptr, nstride, nn, nkeep = _cloud_rows(self._normals)
+        if nn != n or nstride < 16:
+            raise ValueError("SampleConsensusModelCylinder: the normals must be (n, >= 4) records (nx, ny, nz, curvature), "
+                             "one per record of the cloud")
+        ip, ni, ikeep = (None, 0, None) if self._indices is None else _index_list(self._indices)
+        return ptr, n, stride, nptr, nstride, ip, ni, (keep, nkeep, ikeep)
+
+    def _set_size(self, n, ni):
+        return ni if self._indices is not None else n
+
+    @staticmethod
+    def _coeff(coeff):
+        c = np.ascontiguousarray(coeff, np.float32).reshape(-1)
+        if len(c) != 7:  # sac_model.h: isModelValid refuses another size
+            raise ValueError("SampleConsensusModelCylinder: 7 coefficients (line_pt, line_dir, radius), got %d" % len(c))
+        return c
+
+    def computeModelCoefficients(self, samples):
+        """-> the 7 coefficients of the two samples (cloud indices, in this order), or None where the reference returns false
+        (identical points, a radius outside the limits)"""
+        ptr, n, stride, nptr, nstride, ip, ni, keep = self._inputs()
+        s = np.ascontiguousarray(samples, np.int32).reshape(-1)
+        if len(s) != 2:  # :52-56
+            raise ValueError("SampleConsensusModelCylinder: a sample holds 2 indices, got %d" % len(s))
+        coeff = np.zeros(7, np.float32)
+        found = C.c_int(0)
+        check(self.lib.pclhip_sac_cylinder_model(self.ctx.h, ptr, n, stride, nptr, nstride,
+                                                 s.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.m), _fp(coeff),
+                                                 C.byref(found)), self.ctx.h)
+        return coeff if found.value else None
+
+    def evaluate(self, coeffs, threshold):
+        """countWithinDistance and isModelValid of (H, 7) coefficient rows -> ((H,) uint32 counts, (H,) bool valid)"""
+        ptr, n, stride, nptr, nstride, ip, ni, keep = self._inputs()
+        M = np.ascontiguousarray(coeffs, np.float32).reshape(-1, 7)
+        cnt = np.zeros(len(M), np.uint32)
+        valid = np.ones(len(M), np.uint8)
+        check(self.lib.pclhip_sac_cylinder_evaluate(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni, float(threshold),
+                                                    C.byref(self.m), _fp(M), len(M), C.c_void_p(cnt.ctypes.data),
+                                                    C.c_void_p(valid.ctypes.data)), self.ctx.h)
+        return cnt, valid.astype(bool)
+
+    def countWithinDistance(self, coeff, threshold):
+        return int(self.evaluate(self._coeff(coeff), threshold)[0][0])
+
+    def selectWithinDistance(self, coeff, threshold):
+        """-> the inliers (cloud indices in the point set's order), int32: a torch tensor for a torch cloud"""
+        ptr, n, stride, nptr, nstride, ip, ni, keep = self._inputs()
+        c = self._coeff(coeff)
+        m = max(self._set_size(n, ni), 1)
+        if _is_torch(self._cloud):
+            import torch
+            inl = torch.empty(m, dtype=torch.int32, device=self._cloud.device)
+            pin = C.c_void_p(inl.data_ptr())
+        else:
+            inl = np.empty(m, np.int32)
+            pin = C.c_void_p(inl.ctypes.data)
+        n_in = C.c_uint64(0)
+        check(self.lib.pclhip_sac_cylinder_select(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni, float(threshold),
+                                                  C.byref(self.m), _fp(c), pin, m, C.byref(n_in)), self.ctx.h)
+        return inl[:n_in.value]
+
+    def getDistancesToModel(self, coeff):
+        """-> (n,) float64, one per entry of the point set; empty for a model that fails isModelValid"""
+        ptr, n, stride, nptr, nstride, ip, ni, keep = self._inputs()
+        c = self._coeff(coeff)
+        m = max(self._set_size(n, ni), 1)
+        dist = np.empty(m, np.float64)
+        n_out = C.c_uint64(0)
+        check(self.lib.pclhip_sac_cylinder_distances(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni, C.byref(self.m), _fp(c),
+                                                     C.c_void_p(dist.ctypes.data), m, C.byref(n_out)), self.ctx.h)
+        return dist[:n_out.value]
+
+    def optimizeModelCoefficients(self, inliers, coeff):
+        """-> the refined coefficients (the given ones where nothing was refined); lastOptimize() tells which"""
+        assert self._cloud is not None, "the model has no cloud"
+        ptr, stride, n, keep = _cloud(self._cloud)
+        c = self._coeff(coeff)
+        ip, ni, ikeep = _index_list(inliers)
+        out = np.zeros(7, np.float32)
+        refined, iters = C.c_int(0), C.c_int(0)
+        check(self.lib.pclhip_sac_cylinder_optimize(self.ctx.h, ptr, n, stride, ip, ni, C.byref(self.m), _fp(c), _fp(out),
+                                                    C.byref(refined), C.byref(iters)), self.ctx.h)
+        self._last_optimize = dict(refined=bool(refined.value), iterations=int(iters.value))
+        return out
+
+    def lastOptimize(self):
+        """dict(refined, iterations: Levenberg-Marquardt steps tried) of the last optimizeModelCoefficients()"""
+        return getattr(self, "_last_optimize", None)
+
+
+class RandomSampleConsensus:
+    """pcl::RandomSampleConsensus<PointT> (sample_consensus/include/pcl/sample_consensus/ransac.h, impl/ransac.hpp:56-217) for a
+    SampleConsensusModelCylinder, over pclhip_sac_cylinder_segment without the refit.  The draws are a pure function of
+    (seed, trial, slot): setSeed.  Not built: refineModel, setNumberOfThreads (the trials are scored in batches on the
+    device)."""
+
+    def __init__(self, model, threshold=None):
+        if not isinstance(model, SampleConsensusModelCylinder):
+            raise NotImplementedError("RandomSampleConsensus: only SampleConsensusModelCylinder is built")
+        self.model = model
+        self.ctx = model.ctx
+        self.lib = model.lib
+        self.p = _lib.SacPlaneParams()
+        self.lib.pclhip_sac_plane_params_default(C.byref(self.p))
+        self.p.optimize_coefficients = 0
+        self.p.max_iterations = 10000       # ransac.h:90,101
+        self.p.distance_threshold = float(np.finfo(np.float64).max) if threshold is None else float(threshold)
+        self._reset()
+
+    def _reset(self):
+        self._inliers = None
+        self._coeff = np.zeros(0, np.float32)
+        self._sample = []
+        self._stats = None
+
+    def setDistanceThreshold(self, threshold):
+        self.p.distance_threshold = float(threshold)
+
+    def getDistanceThreshold(self):
+        return float(self.p.distance_threshold)
+
+    def setMaxIterations(self, n):
+        self.p.max_iterations = int(n)
+
+    def getMaxIterations(self):
+        return int(self.p.max_iterations)
+
+    def setProbability(self, probability):
+        self.p.probability = float(probability)
+
+    def getProbability(self):
+        return float(self.p.probability)
+
+    def setSeed(self, seed):
+        self.p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def setBatchSize(self, n):
+        """Trials per scoring pass (0: automatic); never changes a result."""
+        self.p.batch_size = int(n)
+
+    def refineModel(self, *a, **k):
+        raise NotImplementedError("RandomSampleConsensus: refineModel is not built")
+
+    def setNumberOfThreads(self, *a, **k):
+        raise NotImplementedError("RandomSampleConsensus: setNumberOfThreads is not built")
+
+    def _segment(self, optimize):
+        """pclhip_sac_cylinder_segment -> (found, inliers, outliers, coefficients, stats)"""
+        md = self.model
+        ptr, n, stride, nptr, nstride, ip, ni, keep = md._inputs()
+        m = max(md._set_size(n, ni), 1)
+        if _is_torch(md._cloud):
+            import torch
+            inl = torch.empty(m, dtype=torch.int32, device=md._cloud.device)
+            outl = torch.empty(m, dtype=torch.int32, device=md._cloud.device)
+            pin, pout = C.c_void_p(inl.data_ptr()), C.c_void_p(outl.data_ptr())
+        else:
+            inl, outl = np.empty(m, np.int32), np.empty(m, np.int32)
+            pin, pout = C.c_void_p(inl.ctypes.data), C.c_void_p(outl.ctypes.data)
+        coeff = np.zeros(7, np.float32)
+        n_in, n_out = C.c_uint64(0), C.c_uint64(0)
+        st = _lib.SacPlaneStats()
+        p = _lib.SacPlaneParams.from_buffer_copy(self.p)
+        p.optimize_coefficients = int(bool(optimize))
+        rc = self.lib.pclhip_sac_cylinder_segment(self.ctx.h, ptr, n, stride, nptr, nstride, ip, ni, C.byref(p), C.byref(md.m),
+                                                  _fp(coeff), pin, m, C.byref(n_in), pout, m, C.byref(n_out), C.byref(st))
+        check(rc, self.ctx.h)
+        stats = dict(trials=int(st.trials), iterations=int(st.iterations), skipped=int(st.skipped), batches=int(st.batches),
+                     best_trial=int(st.best_trial), best_count=int(st.best_count), refined=bool(st.refined),
+                     count_ms=float(st.count_ms), total_ms=float(st.total_ms), n_inliers=int(n_in.value),
+                     n_outliers=int(n_out.value))
+        return st.best_trial >= 0, inl[:n_in.value], outl[:n_out.value], coeff, stats
+
+    def computeModel(self):
+        """-> True when a model was found (ransac.hpp:204-216)"""
+        self._reset()
+        found, inl, outl, coeff, stats = self._segment(False)
+        self._stats = stats
+        if not found:
+            return False
+        self._inliers, self._coeff = inl, coeff
+        tr = self.trace(stats["best_trial"] + 1)
+        if len(tr) > stats["best_trial"]:
+            pos = tr[stats["best_trial"]]["samples"]
+            ids = self.model._indices
+            self._sample = [int(ids[p]) for p in pos] if ids is not None else [int(p) for p in pos]
+        return True
+
+    def segment(self, optimize=True):
+        """What SACSegmentation::segment does with this model and method in ONE call (sac_segmentation.hpp:79-133):
+        computeModel, optimizeModelCoefficients, selectWithinDistance -> (inliers, coefficients [7], outliers); empty lists
+        and coefficients when no model was found"""
+        found, inl, outl, coeff, stats = self._segment(optimize)
+        self._stats = stats
+        if not found:
+            return inl[:0], np.zeros(0, np.float32), outl
+        return inl, coeff, outl
+
+    def getModel(self):
+        """The winner's sample (cloud indices)."""
+        return list(self._sample)
+
+    def getInliers(self):
+        return self._inliers if self._inliers is not None else np.zeros(0, np.int32)
+
+    def getModelCoefficients(self):
+        return self._coeff
+
+    def stats(self):
+        """dict of the last computeModel() / segment(): trials, iterations, skipped, batches, best_trial, best_count, refined,
+        count_ms, total_ms, n_inliers, n_outliers"""
+        return self._stats
+
+    def trace(self, capacity=65536):
+        """One dict per trial the last call consumed: samples (positions in the point set), skipped, coefficients, count,
+        valid"""
+        n = C.c_uint64(0)
+        check(self.lib.pclhip_sac_last_cylinder_trace(self.ctx.h, None, 0, C.byref(n)), self.ctx.h)
+        m = min(int(n.value), int(capacity))
+        buf = (_lib.SacCylinderTrace * max(1, m))()
+        check(self.lib.pclhip_sac_last_cylinder_trace(self.ctx.h, buf, m, C.byref(n)), self.ctx.h)
+        return [dict(samples=list(t.samples), skipped=bool(t.skipped), coefficients=np.array(t.coefficients, np.float32),
+                     count=int(t.count), valid=bool(t.valid)) for t in buf[:m]]
+
+
 def featureKSearch(ctx, target_rows, query_rows, k):
     """KdTreeFLANN<FeatureT>::nearestKSearch by exact brute force over pclhip_feature_knn: (n, D) float32 rows, numpy or
     torch device tensors -> (indices (nq, k) int32, d2 (nq, k) float32, counts (nq,) uint32), ascending (d2, index); -1 /

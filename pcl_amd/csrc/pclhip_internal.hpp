@@ -289,6 +289,7 @@ struct pclhip_ctx {
   // the trials the last pclhip_sac_segment_plane consumed (sac.hpp; pclhip_sac_last_trace)
   std::vector<pclhip_sac_plane_trace> sac_trace;
   std::vector<uint8_t> sac_trace_valid;  // the gate's bit of each (sac_models.hpp; pclhip_sac_last_model_trace)
+  std::vector<pclhip_sac_cylinder_trace> sac_cylinder_trace;  // of the last pclhip_sac_cylinder_segment (sac_cylinder.hpp)
   // the trials the last pclhip_correspondence_rejector_sample_consensus consumed (rejector_sac.hpp)
   std::vector<pclhip_rejector_sac_trace> rejsac_trace;
 };

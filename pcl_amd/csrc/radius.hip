@@ -453,6 +453,8 @@ static pclhip_status normals_radius_impl(pclhip_index* ix, const float4* queries
 #include "sac.hpp"
 // ... its constrained planes (a gate per hypothesis) and SACSegmentationFromNormals' plane (the distance with the normals)
 #include "sac_models.hpp"
+// SampleConsensusModelCylinder under RandomSampleConsensus: two oriented points, the distance with the normals, an LM refit
+#include "sac_cylinder.hpp"
 
 // SampleConsensusPrerejective: its scoring pass is a bounded 1-NN traversal of the target index
 #include "scp.hpp"

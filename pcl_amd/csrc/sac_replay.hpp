@@ -15,6 +15,7 @@ struct Replay {
   int max_iterations = 50;
   double log_probability = 0.0;   // log(1 - probability)
   double one_over_n = 0.0;
+  int sample_size = 3;            // the model's: the exponent of the stopping rule (2 for the cylinder)
   int iterations = 0;
   uint32_t skipped = 0;
   uint32_t best = 0;
@@ -23,8 +24,9 @@ struct Replay {
   uint64_t trials = 0;            // trials fed so far
   bool done = false;
 
-  void start(int max_it, double probability, uint64_t n) {
+  void start(int max_it, double probability, uint64_t n, int samples = 3) {
     *this = Replay();
+    sample_size = samples;
     max_iterations = max_it;
     log_probability = std::log(1.0 - probability);
     one_over_n = 1.0 / double(n);
@@ -42,7 +44,7 @@ struct Replay {
       best = count;
       best_trial = trial;
       const double w = double(best) * one_over_n;
-      double p_outliers = 1.0 - std::pow(w, 3.0);
+      double p_outliers = 1.0 - std::pow(w, double(sample_size));
       p_outliers = p_outliers > DBL_EPSILON ? p_outliers : DBL_EPSILON;
       p_outliers = p_outliers < 1.0 - DBL_EPSILON ? p_outliers : 1.0 - DBL_EPSILON;
       k = log_probability / std::log(p_outliers);
