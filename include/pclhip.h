@@ -643,7 +643,9 @@ PCLHIP_API pclhip_status pclhip_icp_set_reciprocal(pclhip_icp* icp, int enable);
  * Refused: refine != 0 (refineModel is a host loop of up to 1,000 data-dependent rounds with a median per round:
  * PCLHIP_ERR_INVALID with a message); duplicate query indices and indices outside a cloud (PCLHIP_ERR_INVALID);
  * max_iterations above 1,000,000 or negative, a threshold that is negative or NaN, a probability outside ]0, 1[
- * (PCLHIP_ERR_INVALID); the chain kind under multi-GPU iterations (PCLHIP_ERR_STATE).  Not built:
+ * (PCLHIP_ERR_INVALID); the chain kind over a source whose index list (pclhip_icp_set_source_indexed) names a record
+ * twice -- the same duplicate query indices, refused when the chain is applied (PCLHIP_ERR_INVALID; the other kinds take
+ * such a source as before); the chain kind under multi-GPU iterations (PCLHIP_ERR_STATE).  Not built:
  * CorrespondenceRejectorSampleConsensus2D.
  *
  * In the chain: pclhip_rejector.param = inlier threshold, .min_correspondences = max_iterations, .reserved = seed;

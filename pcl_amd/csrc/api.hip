@@ -342,6 +342,20 @@ __global__ void check_indices_kernel(const int32_t* __restrict__ sel, uint64_t m
   }
 }
 
+// one pass over a bitmap of the cloud (zero before the launch): *repeated = 1 when an index is named twice; an index outside
+// the cloud is check_indices_kernel's to report
+__global__ void repeated_indices_kernel(const int32_t* __restrict__ sel, uint64_t m, uint64_t n, uint32_t* __restrict__ bitmap,
+                                        int* __restrict__ repeated) {
+  const uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;
+  if (i < m) {
+    const int32_t v = sel[i];
+    if (v >= 0 && uint64_t(v) < n) {
+      const uint32_t bit = 1u << (uint32_t(v) & 31u);
+      if (atomicOr(&bitmap[uint32_t(v) >> 5], bit) & bit) *repeated = 1;  // (every writer stores the same value)
+    }
+  }
+}
+
 __global__ void transform_cloud_kernel(Mat44 T, int order, const void* in, void* out, size_t stride, uint64_t n,
                                        size_t nrm_off) {
   const uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x;
@@ -1718,24 +1732,36 @@ pclhip_status pclhip_icp_set_source_indexed(pclhip_icp* icp, const void* points,
     }
   }
   const void* dsel = nullptr;
+  bool src_repeats = false;
   if (indices) {  // PCLBase::setIndices / setIndicesSource: only these points take part
     PCLHIP_REQUIRE(ctx, n_indices < 0x7FFFFFFFull, "too many indices");
     st = to_device(ctx, indices, size_t(n_indices) * sizeof(int32_t), &dsel, &owned);
     if (st != PCLHIP_OK) return st;
     guard.add(owned);
     if (n_indices > 0) {
+      // bad[0]: an index outside the cloud (refused); bad[1]: an index named twice (kept for the SampleConsensus rejector,
+      // which refuses such a source: rejector_sac.hpp)
       int* bad = nullptr;
-      PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &bad, sizeof(int)));
+      uint32_t* bitmap = nullptr;
+      const size_t words = (size_t(n) + 31) / 32 + 1;  // (never an empty allocation)
+      PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &bad, 2 * sizeof(int)));
       guard.add(bad);
-      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+      PCLHIP_CHECK_HIP(ctx, dev_malloc(ctx, &bitmap, words * 4));
+      guard.add(bitmap);
+      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(bad, 0, 2 * sizeof(int), ctx->stream));
+      PCLHIP_CHECK_HIP(ctx, hipMemsetAsync(bitmap, 0, words * 4, ctx->stream));
       hipLaunchKernelGGL(check_indices_kernel, dim3(unsigned((n_indices + 255) / 256)), dim3(256), 0, ctx->stream,
                          static_cast<const int32_t*>(dsel), n_indices, n, bad);
-      int hbad = 0;
-      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      hipLaunchKernelGGL(repeated_indices_kernel, dim3(unsigned((n_indices + 255) / 256)), dim3(256), 0, ctx->stream,
+                         static_cast<const int32_t*>(dsel), n_indices, n, bitmap, bad + 1);
+      int hbad[2] = {0, 0};
+      PCLHIP_CHECK_HIP(ctx, hipMemcpyAsync(hbad, bad, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
       PCLHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      PCLHIP_REQUIRE(ctx, hbad == 0, "indices must lie in [0, n)");
+      PCLHIP_REQUIRE(ctx, hbad[0] == 0, "indices must lie in [0, n)");
+      src_repeats = hbad[1] != 0;
     }
   }
+  icp->src_repeats = src_repeats;
   const uint64_t m = indices ? n_indices : n;
   icp->n_orig = n;
   icp->n = uint32_t(m);

@@ -348,6 +348,7 @@ struct pclhip_icp {
   uint64_t n_orig = 0;       // source records
   uint32_t n = 0;            // source points (all records; non-finite ones are flagged invalid)
   uint32_t n_finite = 0;     // ... of which finite: the front of the kd-ordered arrays
+  bool src_repeats = false;  // the source's index list names a record twice (pclhip_icp_set_source_indexed)
   // the staged device copy of a HOST source cloud's records (all fields), kept for pclhip_icp_transform_source
   void* src_records = nullptr;
   const void* src_records_host = nullptr;

@@ -539,6 +539,10 @@ pclhip_status rsac_apply_chain(pclhip_icp* icp, A& g, const pclhip_rejector& r) 
   R.batch_size = 0;
   pclhip_status rc = rsac_checked_run(ctx, R);
   if (rc != PCLHIP_OK) return rc;
+  // two slots with one original index: the scan below would count one pair and the scoring pass two, and with as many
+  // indices as records an original index without a slot would leave by_orig unwritten
+  PCLHIP_REQUIRE(ctx, !icp->src_repeats,
+                 "SampleConsensus rejector: a source index is listed twice (the reference would silently keep the last pair)");
   if (!icp->rejsac_host) {
     PCLHIP_CHECK_HIP(ctx, pinned_malloc(ctx, &icp->rejsac_host, sizeof(RejSacState)));
     std::memset(icp->rejsac_host, 0, sizeof(RejSacState));

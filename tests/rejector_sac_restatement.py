@@ -160,6 +160,74 @@ def count_within(T, src_pts, tgt_pts, threshold):
     return int(np.count_nonzero(within(T, src_pts, tgt_pts, threshold)))
 
 
+# ---- the score at its bound: what a test places pairs with, and what a wrong kernel would compute ---------------------------------
+def float_bound(threshold):
+    """rejector_sac.hpp: rsac_float_bound -- the largest float32 whose double lies below threshold * threshold, so that
+    double(d2) < threshold * threshold  <=>  d2 <= float_bound(threshold); NaN for a NaN threshold"""
+    t2 = float(threshold) * float(threshold)
+    if t2 != t2:
+        return F(np.nan)
+    with np.errstate(all="ignore"):
+        f = np.finfo(F).max if t2 > float(np.finfo(F).max) else F(t2)
+        while float(f) >= t2:
+            f = np.nextafter(f, F(-np.inf))
+    return F(f)
+
+
+def thresholds_around(v):
+    """the adjacent doubles t_lo < t_hi with t_lo * t_lo <= double(v) < t_hi * t_hi for a finite float32 v >= 0, by bisection
+    over the double's bits (the rounded product of a double with itself never falls as the double grows): under t_lo a pair
+    with d2 == v is outside, under t_hi it is inside, and no double lies between the two"""
+    v = float(F(v))
+    assert 0.0 <= v < math.inf
+    lo, hi = 0, int(np.float64(np.inf).view(np.uint64))  # lo * lo <= v < hi * hi throughout
+    as_double = lambda b: float(np.uint64(b).view(np.float64))  # noqa: E731
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        t = as_double(mid)
+        if t * t <= v:
+            lo = mid
+        else:
+            hi = mid
+    return as_double(lo), as_double(hi)
+
+
+def _fma(a, b, c):
+    """fl32(a * b + c) with the product unrounded: the product of two float32 is exact in float64, the sum is rounded to
+    float64 and then to float32 (a double rounding that differs from a true fused multiply-add only on a float64 tie)"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
+
+
+def pair_d2_contracted(T, src_pts, tgt_pts):
+    """pair_d2 as a compiler that contracts would build it: every `x + a * b` of the stated order is one fused multiply-add
+    (only the first product of a sum is rounded on its own).  NOT the contract: a kernel that computes this is wrong."""
+    T = np.asarray(T, F)
+    s, t = np.asarray(src_pts, F), np.asarray(tgt_pts, F)
+    with np.errstate(all="ignore"):
+        e = []
+        for r in range(3):
+            p = _fma(np.broadcast_to(T[r, 1], s[:, 1].shape), s[:, 1], T[r, 0] * s[:, 0])
+            p = _fma(np.broadcast_to(T[r, 2], s[:, 2].shape), s[:, 2], p)
+            e.append((p + T[r, 3]) - t[:, r])
+        return _fma(e[1], e[1], _fma(e[2], e[2], e[0] * e[0]))
+
+
+def pair_d2_reordered(T, src_pts, tgt_pts):
+    """pair_d2 with the squares summed in axis order, d2 = (e.x e.x + e.y e.y) + e.z e.z.  NOT the contract either."""
+    T = np.asarray(T, F)
+    s, t = np.asarray(src_pts, F), np.asarray(tgt_pts, F)
+    with np.errstate(all="ignore"):
+        e = [(((T[r, 0] * s[:, 0] + T[r, 1] * s[:, 1]) + T[r, 2] * s[:, 2]) + T[r, 3]) - t[:, r] for r in range(3)]
+        return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
+
+
+def counts_with(d2_of, transforms, src_pts, tgt_pts, threshold):
+    """the counts of several transforms under one of the d2 expressions above -> (H,) int64"""
+    t2 = float(threshold) * float(threshold)
+    with np.errstate(all="ignore"):
+        return np.array([np.count_nonzero(d2_of(T, src_pts, tgt_pts).astype(np.float64) < t2) for T in transforms], np.int64)
+
+
 # ---- the loop --------------------------------------------------------------------------------------------------------------------
 class Replay:
     """ransac.hpp:154-201 on a sequence of counts: sac_replay.hpp's rule without its skip branch"""

@@ -113,23 +113,28 @@ def edge_margin(trace, s, seed, thresh):
     return worst
 
 
-def check_against_restatement(r, src, tgt, q, m, threshold, max_iterations, seed, out):
+def check_against_restatement(r, src, tgt, q, m, threshold, max_iterations, seed, out, margins=("k", "threshold", "edge")):
     """the device's run against the restatement on the device's own transforms, after the restatement alone has shown that
-    no float order and no libm can matter on this scene"""
+    no float order and no libm can matter on this scene.  margins: which of those three assertions are made (all, unless a
+    case of tests/test_gpu_rejector_sac_regimes.py states why one cannot hold on its scene)"""
     rq, rm, pos, T, st, trace = out
     s, t = src[q], tgt[m]
     own = rr.reject(src, tgt, q, m, threshold, max_iterations, seed=seed)
-    assert own["k_margin"] > 64 * 2.0 ** -52, "a trial's iteration count within 64 ulps of k: choose another scene"
-    assert rr.threshold_margin(own["trace"], s, t, threshold) > 1e-6, "a pair within 1e-6 of threshold^2"
+    if "k" in margins:
+        assert own["k_margin"] > 64 * 2.0 ** -52, "a trial's iteration count within 64 ulps of k: choose another scene"
+    if "threshold" in margins:
+        assert rr.threshold_margin(own["trace"], s, t, threshold) > 1e-6, "a pair within 1e-6 of threshold^2"
     if own["sample_dist_thresh"] > 0:
-        assert edge_margin(own["trace"], s, seed, own["sample_dist_thresh"]) > 1e-4, "an edge within 1e-4 of the sample threshold"
+        if "edge" in margins:
+            assert edge_margin(own["trace"], s, seed, own["sample_dist_thresh"]) > 1e-4, "an edge within 1e-4 of the sample threshold"
         assert abs(st["sample_dist_thresh"] - own["sample_dist_thresh"]) <= 1e-5 * own["sample_dist_thresh"]
     assert len(trace) == own["trials"] == st["trials"]
     for d, w in zip(trace, own["trace"]):
         assert d["samples"] == w["samples"] and d["attempts"] == w["attempts"] and d["no_sample"] == w["no_sample"]
     ref = rr.reject(src, tgt, q, m, threshold, max_iterations, seed=seed,
                     transforms={i: d["transformation"] for i, d in enumerate(trace)})
-    assert rr.threshold_margin(ref["trace"], s, t, threshold) > 1e-6
+    if "threshold" in margins:
+        assert rr.threshold_margin(ref["trace"], s, t, threshold) > 1e-6
     worst_R = worst_t = 0.0
     for d, w in zip(trace, ref["trace"]):
         if d["no_sample"]:

@@ -148,3 +148,63 @@ def test_result_rules_and_the_bunny_run():
     r2 = rr.reject(src, tgt, co[:, 0], co[:, 1], threshold=0.01, max_iterations=1000, seed=0,
                    transforms={i: t["T"] for i, t in enumerate(r["trace"])})
     assert np.array_equal(r2["remaining"], r["remaining"]) and r2["iterations"] == r["iterations"]
+
+
+def test_float_bound_agrees_with_within_on_the_floats_around_it():
+    """rsac_float_bound restated: double(d2) < threshold * threshold  <=>  d2 <= float_bound(threshold), on the bound, on the
+    floats either side of it and on 0, the denormals, FLT_MAX and inf"""
+    top = np.finfo(F).max
+    zero3 = np.zeros((1, 3), F)
+    for thr in (0.0, 1e-30, 1e-20, 0.01, 0.25, 1e19, 1e30):
+        b = rr.float_bound(thr)
+        t2 = float(thr) * float(thr)
+        around = [b]
+        with np.errstate(all="ignore"):
+            for _ in range(3):
+                around = [np.nextafter(around[0], F(-np.inf))] + around + [np.nextafter(around[-1], F(np.inf))]
+            for d2 in around + [F(0), F(1e-45), np.finfo(F).tiny, top, F(np.inf)]:
+                assert (float(d2) < t2) == bool(d2 <= b), (thr, d2)
+            assert float(b) < t2 or thr == 0.0
+            assert float(np.nextafter(b, F(np.inf))) >= t2 or b == top
+        # ... and through within(): a pair at distance sqrt(d2) along x under the identity, for the d2 that are float squares
+        for root in (F(np.sqrt(b)) if b > 0 else F(0), F(thr) if thr < 1e19 else F(1e19)):
+            with np.errstate(all="ignore"):
+                d2 = F(root * root)
+                got = bool(rr.within(np.eye(4, dtype=F), zero3, np.array([[root, 0, 0]], F), thr)[0])
+            assert got == bool(d2 <= b) == (float(d2) < t2), (thr, root)
+    assert rr.float_bound(0.0) == F(-1e-45) and rr.float_bound(1e-30) == 0 and rr.float_bound(1e30) == top
+    assert np.isnan(rr.float_bound(float("nan")))
+
+
+def test_thresholds_around_a_float():
+    for v in (F(0.0625), F(1e-4), F(2.0 ** -140), np.finfo(F).max, F(0.0), F(1e-45), F(3.0), F(0.01) * F(0.01)):
+        lo, hi = rr.thresholds_around(v)
+        assert lo * lo <= float(v) < hi * hi and np.nextafter(lo, np.inf) == hi
+        if v > 0:
+            assert rr.float_bound(hi) == v and rr.float_bound(lo) == np.nextafter(v, F(-np.inf))
+    assert rr.thresholds_around(F(0.0625))[0] == 0.25 and rr.thresholds_around(F(4.0))[0] == 2.0
+
+
+def test_the_wrong_kernels_differ_from_the_contract_on_the_dense_scene():
+    """the contracted and the reordered d2 are what tests/test_gpu_rejector_sac_regimes.py must be able to tell from the
+    stated one: on its scene they move pairs across threshold^2, elsewhere they stay within a few ulps of it"""
+    from test_gpu_rejector_sac_regimes import dense_scene
+    for thr in (0.02, 0.05, 0.25):
+        src, tgt, q, m, Ts = dense_scene(thr)
+        assert Ts.shape == (70, 4, 4) and len({T.tobytes() for T in Ts}) == 70 and np.abs(Ts - Ts[0]).max() < 1e-5
+        d2 = rr.pair_d2(Ts[0], src, tgt)
+        for wrong in (rr.pair_d2_contracted, rr.pair_d2_reordered):
+            w = wrong(Ts[0], src, tgt)
+            assert (w != d2).any() and np.abs(w.astype(np.float64) - d2).max() <= 1e-4 * thr * thr
+            flipped = (w.astype(np.float64) < thr * thr) != (d2.astype(np.float64) < thr * thr)
+            print("threshold %g, %s: %d of %d pairs change sides under T" % (thr, wrong.__name__, int(flipped.sum()), len(q)))
+        want = rr.counts_with(rr.pair_d2, Ts, src, tgt, thr)
+        assert want.tolist() == [rr.count_within(T, src, tgt, thr) for T in Ts]
+        assert (rr.counts_with(rr.pair_d2_contracted, Ts, src, tgt, thr) != want).any()
+        assert (rr.counts_with(rr.pair_d2_reordered, Ts, src, tgt, thr) != want).any()
+    # exact products and sums: nothing to contract, nothing to reorder
+    s = np.array([[1, 2, 3], [0.5, -4, 8]], F)
+    t = np.array([[2, 2, 2], [1, 1, 1]], F)
+    I = np.eye(4, dtype=F)
+    assert rr.pair_d2(I, s, t).tolist() == rr.pair_d2_contracted(I, s, t).tolist() == rr.pair_d2_reordered(I, s, t).tolist() \
+        == [2.0, 74.25]

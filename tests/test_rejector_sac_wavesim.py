@@ -1,7 +1,9 @@
-"""CorrespondenceRejectorSampleConsensus in the CPU tier: the `-m gpu` tests of tests/test_gpu_rejector_sac.py run on the
-wavefront emulation of tests/wavesim (the recipe of tests/test_sac_models_wavesim.py).  The whole module takes seconds
-there, its largest size included, and none of its cases needs torch: nothing is deselected.  The replay's log and pow are
-the host's here, the ballots of the scoring pass and the atomics of the duplicate bitmap are the emulation's."""
+"""CorrespondenceRejectorSampleConsensus in the CPU tier: the `-m gpu` tests of tests/test_gpu_rejector_sac.py and
+tests/test_gpu_rejector_sac_regimes.py run on the wavefront emulation of tests/wavesim (the recipe of
+tests/test_sac_models_wavesim.py).  The first module takes seconds there, its largest size included, and none of its cases
+needs torch: nothing is deselected.  Of the regimes only the device-buffer case (torch) and the case sized from the device's
+CU count (fullgrid) stay on the GPU.  The replay's log and pow and the eigenvalues' cos, sin and atan2 are the host's
+here, the ballots of the scoring pass and the atomics of the duplicate bitmaps are the emulation's."""
 import os
 import shutil
 import subprocess
@@ -27,3 +29,7 @@ def wavesim_lib():
 
 def test_rejector_sac_gpu_tests_on_the_emulation(wavesim_lib):
     on_the_emulation(wavesim_lib, "test_gpu_rejector_sac.py", GPU_ONLY)
+
+
+def test_rejector_sac_regimes_on_the_emulation(wavesim_lib):
+    on_the_emulation(wavesim_lib, "test_gpu_rejector_sac_regimes.py", GPU_ONLY + " and not fullgrid")
