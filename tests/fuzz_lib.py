@@ -126,6 +126,13 @@ def filters_round(ctx, orc, rng, sizes=(1, 50, 3000, 40000, 300000)):
             ok = False; why = "oracle refused, device did not"
         else:
             ok = np.array_equal(out[:, :4], want, equal_nan=True); why = "%d voxels" % len(want)
+            if ok and wide:   # the whole record (normal, curvature, padding) against tests/voxelgrid_restatement.py
+                import voxelgrid_restatement as vr
+                ref = vr.voxelgrid(cloud, leaf, min_points=minpts, field=kw.get("field"), limits=kw.get("limits"),
+                                   negative=kw.get("negative", False), downsample_all_data=vg.getDownsampleAllData(),
+                                   with_layout=False)
+                ok = ref is not None and vr.same_bytes(out, ref["out"])
+                why += ", whole record " + ("ok" if ok else "MISMATCH: " + vr.first_difference(out, ref["out"]) if ref else "refused")
     except pcl_amd.PclHipError as e:
         want, _ = orc.voxelgrid(cloud, leaf, min_points_per_voxel=minpts, **kw)
         ok = want is None; why = "both refuse (overflow)" if ok else "device refused: %s" % e
